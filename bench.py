@@ -32,10 +32,15 @@ RCCL gather to rank 0, unpack), which tests/test_dist.py drives with host ops ov
 lookahead the timed region holds exactly the prepasses of its own batches: the last warm-up
 batch and the last timed batch queue no ahead prepass.
 
-Prints ONE JSON line on rank 0 (driver contract), with "roofline" for the dominant
-kernel (tracescreen, timed by HIP events on its own stream in a pass with one batch in
-flight, so launches do not overlap) and "cpu_baseline" (the C oracle on the host cores, rank 0
-at N=1 only; its frame is also compared with the GPU's: config.parity).
+Prints ONE JSON line on rank 0 (driver contract).  A plain run does what that line's headline
+needs and no more: it counts one instrumented frame's rays, warms up, times the --steps frames,
+writes --dump-outputs (the last timed batch's first and last framebuffer as .npy) and prints
+metric / value / unit / ms_per_step with the run's config.  --full adds every other pass, after
+the timed loop: config.frame_latency_ms, the config.* companions above, config.verify,
+"roofline" for the dominant kernel (tracescreen, timed by HIP events on its own stream in a pass
+with one batch in flight, so launches do not overlap; its HBM traffic by PMC child processes) and
+"cpu_baseline" (the C oracle on the host cores, rank 0 at N=1 only; its frame is also compared
+with the GPU's: config.parity).
 """
 import argparse
 import json
@@ -115,6 +120,18 @@ def parse():
     ap.add_argument("--graph", type=int, default=None,
                     help="1 = every slot replays its frame as captured hipGraphs (RT_DEVICE_GRAPH), 0 = direct "
                          "launches; default: on for c5 (BASELINE's hipGraph-captured frame loop), off otherwise")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed loop also run everything else the benchmark measures or checks: the "
+                         "instrumented batch (noise lane utilisation), the roofline pass and its HBM traffic, the "
+                         "companion configs, the CPU baseline with the oracle parity of the timed frames, and "
+                         "config.verify.  Off by default: a plain run sets up, warms up, times --steps frames, "
+                         "writes --dump-outputs and prints the result line.  The options below that switch "
+                         "these parts off or tune them act only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed loop rank 0 writes what the loop's last batch computed, the RGBA8 "
+                         "framebuffers of its first and last frame as read back by the caller, to "
+                         "DIR/<name>.npy (float32; a frame over its share of 64 MB as a fixed, seeded sample "
+                         "of its pixels)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-companions", action="store_true",
                     help="skip config.single_frame / config.ref_semantics (extra timed passes)")
@@ -123,8 +140,8 @@ def parse():
                          "many seconds (0 = skip)")
     ap.add_argument("--verify", action="store_true",
                     help="after the timed loop rank 0 checks every assembled frame of the last batch against a "
-                         "whole-frame render on one device (RGBA8, bit for bit); adds config.verify (always on "
-                         "at N>1)")
+                         "whole-frame render on one device (RGBA8, bit for bit); adds config.verify (with "
+                         "--full always on at N>1)")
     ap.add_argument("--cpu-row-step", type=int, default=None, help="CPU baseline (all cores): every n-th row")
     ap.add_argument("--cpu-threads", type=int, default=0, help="CPU baseline threads (0 = the host's share)")
     ap.add_argument("--traffic", choices=["pmc", "off"], default="pmc",
@@ -167,6 +184,25 @@ def batch_sizes(steps, batch):
     n = -(-steps // batch)
     base, extra = divmod(steps, n)
     return [base + (1 if i < extra else 0) for i in range(n)]
+
+
+DUMP_BYTES = 64 * 1000 * 1000  # --dump-outputs: all files together stay under this
+
+
+def dump_outputs(directory, frames):
+    """--dump-outputs: every (name, (H, W, 4) uint8 framebuffer) as directory/<name>.npy, float32
+    (pixels, 4) in row-major pixel order.  A frame over its equal share of DUMP_BYTES is written as
+    a sample of its pixels, drawn without replacement by a generator seeded with 0 and sorted: the
+    same pixels in every run of the same frame size."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    share = (DUMP_BYTES - 1024 * len(frames)) // len(frames)  # .npy headers: 128 bytes each
+    for name, img in frames:
+        px = img.reshape(-1, img.shape[-1]).astype(np.float32)
+        keep = share // (px.shape[1] * 4)
+        if px.shape[0] > keep:
+            px = px[np.sort(np.random.default_rng(0).choice(px.shape[0], size=keep, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), px)
 
 
 def cpu_baseline(consts, landscape, max_steps, ao, row_step, row_step_1t, threads, gpu_rgba32f, gpu_rgba8,
@@ -430,9 +466,12 @@ def main():
                     "rays": W * H + hits + hits * ao + 1024, "img": img})
         return out
 
-    want_cpu = rank == 0 and world == 1 and not a.no_cpu_baseline
-    progress(rank, f"instrumented batch of {B} + whole frame")
-    counts = frame_counts(a.max_steps, a.ao, keep_frame=want_cpu)
+    want_cpu = a.full and rank == 0 and world == 1 and not a.no_cpu_baseline
+    with_companions = a.full and world == 1 and not a.no_companions
+    # a plain run counts one whole frame's rays (the headline value's numerator); the instrumented
+    # batch feeds the roofline only
+    progress(rank, f"instrumented batch of {B} + whole frame" if a.full else "instrumented whole frame")
+    counts = frame_counts(a.max_steps, a.ao, keep_frame=want_cpu, batch_stats=a.full)
     progress(rank, "counts done")
     rays_per_frame, hits = counts["rays"], counts["hits"]
 
@@ -603,11 +642,15 @@ def main():
     g_last = ((ring.frame // B) - 1) % ring.depth
     last = ring.slots[g_last * B:g_last * B + sizes[-1]]
     timed_frames = []
-    if rank == 0:
+    if rank == 0 and (a.full or a.dump_outputs):
         for f in sorted({0, len(last) - 1}):
             timed_frames.append((f"batch {len(sizes) - 1} frame {f}", last[f][0].readback()))
+    if rank == 0 and a.dump_outputs:
+        # (a one-frame last batch has one frame to write)
+        dump_outputs(a.dump_outputs, [("last_batch_last_frame_rgba8", timed_frames[-1][1])]
+                     + [("last_batch_first_frame_rgba8", img) for _, img in timed_frames[:-1]])
     verify = None
-    if (a.verify or world > 1) and rank == 0:
+    if (a.verify or (a.full and world > 1)) and rank == 0:
         # the last timed batch's frames, assembled from every rank's shards, against one whole frame
         vdev, vter = make(stats=False)
         vter.render_device(0, 1)
@@ -622,30 +665,32 @@ def main():
                 verify.append({"frame": f, "pixels": int(bad.sum()), "tiles": len(tiles),
                                "shards": sorted({t % world for t in tiles}), "first_tiles": tiles[:8]})
 
-    # --- roofline pass: full batches one at a time on slot group 0 (launches do not overlap),
+    # --- roofline pass (--full): full batches one at a time on slot group 0 (launches do not overlap),
     # HIP events around every tracescreen launch on the stream it runs on; also the latency ---
     group0 = ring.slots[:B]
-    progress(rank, "roofline pass")
-    ring.set_profiling(True)
-    ring.kernel_time()
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for i in range(n_full):
-        E.render_batch([t for _, t in group0], rank if world > 1 else 0, world)
+    latency_ms = k_avg_ms = kn = None
+    if a.full:
+        progress(rank, "roofline pass")
+        ring.set_profiling(True)
+        ring.kernel_time()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for i in range(n_full):
+            E.render_batch([t for _, t in group0], rank if world > 1 else 0, world)
+            for d, _ in group0:
+                d.present()
+            progress(rank, f"roofline batch {i + 1}/{n_full} queued")
         for d, _ in group0:
-            d.present()
-        progress(rank, f"roofline batch {i + 1}/{n_full} queued")
-    for d, _ in group0:
-        d.synchronize()
-    progress(rank, "roofline pass done")
-    latency_ms = (time.perf_counter() - t1) / n_full * 1e3
-    kms, kn = ring.kernel_time()
-    ring.set_profiling(False)
-    k_avg_ms = kms / max(1, kn)  # one launch = a batch of B frames
+            d.synchronize()
+        progress(rank, "roofline pass done")
+        latency_ms = (time.perf_counter() - t1) / n_full * 1e3
+        kms, kn = ring.kernel_time()
+        ring.set_profiling(False)
+        k_avg_ms = kms / max(1, kn)  # one launch = a batch of B frames
 
-    # --- companions (N=1): frames rendered one per launch sequence (B = 1) ---
+    # --- companions (--full, N=1): frames rendered one per launch sequence (B = 1) ---
     companions = {}
-    if world == 1 and not a.no_companions:
+    if with_companions:
         d0, ter0 = group0[0]
         torch.cuda.synchronize()
         ts = time.perf_counter()
@@ -680,7 +725,7 @@ def main():
             deferred_fused[kdef] = ddev.deferred_fused() - f0
             ddev.destroy()
     ring.destroy()
-    if world == 1 and not a.no_companions:
+    if with_companions:
         # B = 1 with three frames in flight (D3D11's default maximum frame latency, the reference
         # frame loop's own queue depth): each frame is its own prepass -> k_order -> k_trace ->
         # k_finish on its slot's stream, and the next frame's prepass overlaps this one's tail
@@ -724,7 +769,7 @@ def main():
                         f"frames' setTargetDepths + trace with the next two frames' prepasses inside it; every frame "
                         f"in full, the intermediate ones into frame slots (a DISCARD swap chain), {a.steps} frames")}
 
-    if world == 1 and not a.no_companions and a.config == "c3" and (a.max_steps, a.ao) == (512, 1):
+    if with_companions and a.config == "c3" and (a.max_steps, a.ao) == (512, 1):
         rc = frame_counts(0, 0, batch_stats=False)
         rring = E.FrameRing(W, H, gated=GATED, depth=a.frames_in_flight, gpu=local, theme=a.landscape, camera=camera,
                             time_of_day=0.3, max_steps=0, ao_samples=0, batch=B, lookahead=bool(a.lookahead))
@@ -742,7 +787,7 @@ def main():
             "ms_per_frame": round(dt / a.steps * 1e3, 4), "rays_per_frame": rc["rays"],
             "how": "--config ref: the same frames and batching, uncapped march (tracing.hlsl:68), no AO"}
 
-    if world == 1 and not a.no_companions:
+    if with_companions:
         # a moving camera: every frame of the run distinct (the eye advances 2 units per frame along
         # the view direction and the yaw turns 0.01 rad per frame), batched exactly like the timed
         # loop; rays counted per frame by an instrumented render of each camera, and the run's last
@@ -786,7 +831,7 @@ def main():
                    f"batches {sizes}, cameras written into each slot group before its batch; the last frame "
                    f"against an instrumented single-frame render of its camera"}
 
-    if world == 1 and not a.no_companions and a.sustained_s > 0:
+    if with_companions and a.sustained_s > 0:
         # sustained rate: the timed loop's batches back to back for ~--sustained-s seconds (clocks and
         # power under a long load), a HIP event after every batch on its stream, read once at the end
         n_sus = max(2, int(a.sustained_s * 1e3 / (elapsed / a.steps * 1e3 * B) + 0.5))
@@ -823,10 +868,10 @@ def main():
                    f"({a.frames_in_flight} in flight), HIP event per batch; windows of ~1 s"}
 
     # this rank's tracescreen launch time with its phases; rank 0 reports every rank's (config.per_rank)
-    phases.update({"rank": rank, "tracescreen_kernel_ms": round(k_avg_ms, 4)})
+    phases.update({"rank": rank, **({"tracescreen_kernel_ms": round(k_avg_ms, 4)} if a.full else {})})
     per_rank = [phases]
     if world > 1:
-        t = torch.tensor([elapsed, latency_ms], dtype=torch.float64, device=dev_str if backend == "nccl" else "cpu")
+        t = torch.tensor([elapsed, latency_ms or 0.0], dtype=torch.float64, device=dev_str if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, latency_ms = float(t[0].item()), float(t[1].item())
         per_rank = [None] * world
@@ -834,16 +879,17 @@ def main():
 
     ms_per_frame = elapsed / a.steps * 1e3
     value = rays_per_frame * a.steps / elapsed / 1e6
-    # the timed launch's noise3d: tracescreen's, plus (RT_BENCH_GATED=1: the gated launch, nomadplains) the
-    # batch's prepass rays, which then run inside the same trace kernel
     gated = GATED and a.landscape == "nomadplains"
-    batch_noise = counts["batch_noise"] + (counts["prepass_noise"] if gated else 0)
-    achieved = batch_noise * FLOPS_PER_NOISE3D / (k_avg_ms * 1e-3) / 1e12
-    traffic, traffic_how = None, "not measured (N>1: a rank's launch traces a shard; or --traffic off)"
-    if world == 1 and a.traffic == "pmc":
-        progress(rank, "traffic: rocprofv3 FETCH_SIZE / WRITE_SIZE passes")
-        traffic, traffic_how = measure_traffic(a, B)
-        progress(rank, f"traffic: {traffic}")
+    if a.full:
+        # the timed launch's noise3d: tracescreen's, plus (RT_BENCH_GATED=1: the gated launch, nomadplains) the
+        # batch's prepass rays, which then run inside the same trace kernel
+        batch_noise = counts["batch_noise"] + (counts["prepass_noise"] if gated else 0)
+        achieved = batch_noise * FLOPS_PER_NOISE3D / (k_avg_ms * 1e-3) / 1e12
+        traffic, traffic_how = None, "not measured (N>1: a rank's launch traces a shard; or --traffic off)"
+        if world == 1 and a.traffic == "pmc":
+            progress(rank, "traffic: rocprofv3 FETCH_SIZE / WRITE_SIZE passes")
+            traffic, traffic_how = measure_traffic(a, B)
+            progress(rank, f"traffic: {traffic}")
 
     if rank == 0:
         preset = CONFIGS[a.config]
@@ -867,9 +913,10 @@ def main():
                 "noise3d_per_frame_tracescreen": counts["frame_noise"],
                 # the timed batch's noise3d lane-calls / (64 x their wave iterations): SIMD lane
                 # utilisation of the noise work, counted by the instrumented kernels
-                "noise_lane_utilisation": round(counts["noise_lane_util"], 4) if counts["noise_lane_util"] else None,
-                "noise_lane_utilisation_scope": "instrumented (STATS) kernels, which take the product's code paths "
-                                                "(the primary segment tail included: RT_STATS_PRIMARY_SEG)",
+                **({"noise_lane_utilisation": round(counts["noise_lane_util"], 4) if counts["noise_lane_util"] else None,
+                    "noise_lane_utilisation_scope": "instrumented (STATS) kernels, which take the product's code paths "
+                                                    "(the primary segment tail included: RT_STATS_PRIMARY_SEG)"}
+                   if a.full else {}),
                 "parallelism": "single GPU" if world == 1 else (
                     f"tile-cyclic 32x32 shards x{world} (rotated per frame) + RCCL gather per batch"
                     + (" (shards rendered straight into the packed send buffer)" if plan.direct_pack else "")
@@ -880,7 +927,8 @@ def main():
                 "frame_loop": "hipGraph replay per slot (prepass graph + tracescreen graph)" if a.graph
                               else "direct launches" + (", each batch's prepass queued one batch ahead on the GPU's "
                                                         "side stream (rt_terrain_prepass_ahead)" if plan.lookahead else ""),
-                "frame_latency_ms": round(latency_ms, 4),  # one batch of B frames at a time
+                # one batch of B frames at a time (the roofline pass)
+                **({"frame_latency_ms": round(latency_ms, 4)} if a.full else {}),
                 # per rank: mean / max ms per timed batch of each run_batch phase on the batch's stream
                 # (prepass, all_gather, trace, pack, gather, unpack; waits for the other batch in flight
                 # included), each batch's trace start from the common start barrier, and the rank's
@@ -893,7 +941,9 @@ def main():
                               f"device" if not verify else {"MISMATCH": verify}}
                    if verify is not None else {}),
             },
-            "roofline": {
+        }
+        if a.full:
+            out["roofline"] = {
                 "bound": "valu", "achieved": round(achieved, 3), "peak": PEAK_FP32_VECTOR_TFLOPS, "unit": "TFLOP/s",
                 "frac": round(achieved / PEAK_FP32_VECTOR_TFLOPS, 4), "traffic": traffic,
                 "traffic_how": traffic_how,
@@ -907,8 +957,7 @@ def main():
                                 "prepass inside the trace kernel)" if gated else ")"),
                 "note": "FP32 vector-ALU bound (no MFMA-shaped or HBM-bound work); gfx950 vector FP32 peak "
                         "= FP32 dense matrix peak = 157.3 TFLOP/s",
-            },
-        }
+            }
         if want_cpu:
             consts = G.frame_constants(W, H, euler=euler)
             threads = a.cpu_threads or host_threads()

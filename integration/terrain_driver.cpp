@@ -18,7 +18,7 @@
 //               (cbuffer bytes), SunDirection[3]
 //   out.bin:    W*H*4 bytes RGBA8 (IDevice readback), then 1024 float4 CameraResults
 // Test infrastructure for tests/test_gpu_parity.py::test_cpp_adapter_terrain_sequence; built by
-// integration/Makefile (needs the reference headers, so it is built here and shipped prebuilt).
+// oracle/Makefile's `ref` target into oracle/_ref/ (it needs the reference headers to build, not to run).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>

@@ -10,7 +10,7 @@ mkdir -p "$out"
 for r in $(seq 1 "$rounds"); do
   for v in "$@"; do
     lv=$v; [ "$v" = default ] && lv=
-    RT_LIB_VARIANT=$lv timeout -k 10 120 python3 scripts/with_variant.py bench.py --steps 20 --warmup 5 \
+    RT_LIB_VARIANT=$lv timeout -k 10 120 python3 scripts/with_variant.py bench.py --full --steps 20 --warmup 5 \
       --no-companions --no-cpu-baseline --traffic off > "$out/$v.$r.json" 2> "$out/$v.$r.err" || exit 1
     python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(sys.argv[2], d['value'], d['ms_per_step'], d['roofline']['frac'])" \
       "$out/$v.$r.json" "$v" >> "$out/ab.txt" || exit 1

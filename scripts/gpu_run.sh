@@ -4,9 +4,9 @@
 # Output goes to gpurun_out/<name>/; the call stops at the first failing step (each step has its own
 # time limit; a GPU step that fails, faults or times out ends the call).
 #   tests[=<pytest -k expr>]     python -m pytest tests -m gpu -x (optionally -k); testsall: without -x
-#   bench[=<bench.py args>]      one bench.py line -> bench<i>.json (default args: the driver's default)
+#   bench[=<bench.py args>]      one bench.py --full line -> bench<i>.json (default args: the driver's default)
 #   r4bench[=<args>]             the same command on the round-4 snapshot in _ab/r4 (same-box A/B)
-#   ab=<args>                    bench.py --no-cpu-baseline --traffic off --no-companions <args>: one line
+#   ab=<args>                    bench.py --full --no-cpu-baseline --traffic off --no-companions <args>: one line
 #   r4ab=<args>                  the same on the round-4 snapshot
 #   vtests=<variant>:<-k expr>  the GPU tests (-k) against an A/B build
 #   vbench=<variant>:<args>      bench.py against the A/B build _build/librt_hip_<variant>.so
@@ -19,6 +19,7 @@
 #   vpy=<variant>:<script args>  the same against an A/B build _build/librt_hip_<variant>.so
 set -o pipefail
 cd "$GRAFT_REPO_ROOT" || exit 1
+root=$PWD  # the repository's root
 name=$1; shift
 out=gpurun_out/$name; mkdir -p "$out"
 i=0
@@ -52,14 +53,14 @@ for step in "$@"; do
       if [ $rc -ne 0 ] && { [ $kind = vtests ] || [ $rc -ne 1 ]; }; then tail -40 "$out/tests$i.log"; exit 1; fi;;
     bench|r4bench|ab|r4ab)
       dir=.; [ "${kind:0:2}" = r4 ] && dir=_ab/r4
-      extra=""; [ "${kind#r4}" = ab ] && extra="--no-cpu-baseline --traffic off --no-companions"
+      extra="--full"; [ "${kind#r4}" = ab ] && extra="--full --no-cpu-baseline --traffic off --no-companions"
       (cd $dir && timeout -k 10 600 python3 bench.py $extra $arg) > "$out/bench$i.json" 2> "$out/bench$i.err" \
         || { tail -20 "$out/bench$i.err"; exit 1; }
       summ "$step" "$out/bench$i.json";;
     vbench|gbench)  # vbench=<variant>:<bench args> (an A/B build); gbench=<args>: RT_BENCH_GATED=1
       if [ $kind = vbench ]; then v=${arg%%:*}; rest=${arg#*:}; else v=; rest=$arg; fi
       gt=0; [ $kind = gbench ] && gt=1
-      RT_BENCH_GATED=$gt RT_LIB_VARIANT=$v timeout -k 10 600 python3 scripts/with_variant.py bench.py $rest \
+      RT_BENCH_GATED=$gt RT_LIB_VARIANT=$v timeout -k 10 600 python3 scripts/with_variant.py bench.py --full $rest \
         > "$out/bench$i.json" 2> "$out/bench$i.err" || { tail -20 "$out/bench$i.err"; exit 1; }
       summ "$step" "$out/bench$i.json";;
     sim)
@@ -67,7 +68,7 @@ for step in "$@"; do
       tail -5 "$out/sim$i.log";;
     prof)
       (cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$GRAFT_REPO_ROOT/$out/prof$i" \
-        -o run -- python3 "$GRAFT_REPO_ROOT/bench.py" --no-cpu-baseline --traffic off --no-companions $arg) \
+        -o run -- python3 "$root/bench.py" --full --no-cpu-baseline --traffic off --no-companions $arg) \
         > "$out/prof$i.log" 2>&1 || { tail -20 "$out/prof$i.log"; exit 1; }
       tail -1 "$out/prof$i.log";;
     pyprof)  # pyprof=<script and args>: rocprofv3 --kernel-trace over a python script of the repo -> prof<i>/

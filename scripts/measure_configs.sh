@@ -15,7 +15,7 @@ for c in $CFGS; do
   [ "$c" = "c5" ] && extra="--cpu-row-step 16"
   [ "$c" = "c3" ] && extra="--cpu-row-step 8"
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$c -o run -- \
-    python3 bench.py --config $c --steps 24 --warmup 2 --traffic off $extra > $O/bench_$c.json 2> $O/bench_$c.log
+    python3 bench.py --full --config $c --steps 24 --warmup 2 --traffic off $extra > $O/bench_$c.json 2> $O/bench_$c.log
   rc=$?; echo "$c rc=$rc"; tail -c 600 $O/bench_$c.json
   [ $rc -ne 0 ] && { tail -20 $O/bench_$c.log; exit $rc; }
 done

@@ -3,7 +3,7 @@
 # configs), the driver's command (--steps 20 --warmup 5) and 96 frames, under gpurun_out/final_cfg/.
 cd "$GRAFT_REPO_ROOT"; O=gpurun_out/final_cfg; mkdir -p $O
 run() { local name=$1; shift
-  timeout -k 10 400 python3 bench.py "$@" > $O/$name.json 2> $O/$name.err || { echo "$name failed"; tail -20 $O/$name.err; exit 1; }
+  timeout -k 10 400 python3 bench.py --full "$@" > $O/$name.json 2> $O/$name.err || { echo "$name failed"; tail -20 $O/$name.err; exit 1; }
   python3 -c "import json,sys; d=json.loads(open('$O/$name.json').read().strip().splitlines()[-1]); print('$name', d['value'], d['ms_per_step'], d['roofline']['frac'])"
 }
 run c1 --config c1 && run c2 --config c2 && run c5 --config c5 --cpu-row-step 16 && \

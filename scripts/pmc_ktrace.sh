@@ -9,7 +9,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 O=gpurun_out/$1; mkdir -p $O
 V=${2:-}
 run() { local n=$1; shift
-  RT_LIB_VARIANT=$V timeout -k 10 300 rocprofv3 --pmc "$@" --output-format csv -d $O/$n -o run -- python3 scripts/with_variant.py bench.py \
+  RT_LIB_VARIANT=$V timeout -k 10 300 rocprofv3 --pmc "$@" --output-format csv -d $O/$n -o run -- python3 scripts/with_variant.py bench.py --full \
     --steps 10 --warmup 10 --batch 10 --frames-in-flight 1 --no-cpu-baseline --traffic off --no-companions > $O/$n.log 2>&1
   local rc=$?; echo "$n exit $rc"; return $rc; }
 run p1 SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY && \

@@ -8,7 +8,7 @@ O=gpurun_out/pmcl; rm -rf $O; mkdir -p $O
 for v in "$@"; do
   tag=${v:-default}
   RT_LIB_VARIANT=$v timeout -k 10 240 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS GRBM_GUI_ACTIVE \
-    --output-format csv -d $O/$tag -o run -- python3 scripts/with_variant.py bench.py --steps 10 --warmup 1 --no-cpu-baseline --traffic off --no-companions --frames-in-flight 1 > $O/$tag.log 2>&1 || { echo "pmc $tag failed"; exit 1; }
+    --output-format csv -d $O/$tag -o run -- python3 scripts/with_variant.py bench.py --full --steps 10 --warmup 1 --no-cpu-baseline --traffic off --no-companions --frames-in-flight 1 > $O/$tag.log 2>&1 || { echo "pmc $tag failed"; exit 1; }
   python3 - $O/$tag $tag <<'PY'
 import csv, glob, re, sys, collections
 per = collections.defaultdict(lambda: collections.defaultdict(float))

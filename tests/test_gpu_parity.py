@@ -257,7 +257,7 @@ def test_frame_bitexact_reference_call_sequence(spec):
     dev.destroy()
 
 
-DRIVER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "integration", "_build",
+DRIVER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref",
                       "terrain_driver")
 
 
@@ -272,8 +272,8 @@ def test_cpp_adapter_terrain_sequence(spec, mode, tmp_path):
     CellDistance write -> per tile ThreadOffset write + run + flush -> present), the one-call
     device path, or that path on an RT_DEVICE_DEFERRED device (DeviceHIP::setFlags) over three frames;
     the RGBA8 readback and CameraResults equal the golden frame's."""
-    assert os.path.exists(DRIVER), "integration/_build/terrain_driver not built (make -C integration, needs " \
-                                   "the reference headers: __graft_entry__.build() in the build container)"
+    assert os.path.exists(DRIVER), "oracle/_ref/terrain_driver not built (make -C oracle ref, needs the " \
+                                   "reference headers: __graft_entry__.build() where the reference is present)"
     import subprocess
     gold = GI.load()
     land, pose, w, h, aa, ms, ao = GI.unpack(spec)
