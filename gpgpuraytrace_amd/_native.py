@@ -24,6 +24,8 @@ RT_DEVICE_DEBUG_GATE_STRESS = 512  # ABI 8, diagnostic: L1-warm consumers and a 
 RT_DEVICE_DEFERRED = 1024  # ABI 9: a render's trace launches with the next render (which fuses its prepass into it)
 RT_DEVICE_DEBUG_DEFER_SMALL = 2048  # ABI 9, diagnostic: the one-frame deferral below 1280x720 pixels too (tests)
 ABI_VERSION = 9  # include/frosttrace.h RT_ABI_VERSION this binding's structs and signatures match
+RT_READBACK_RGBA8 = 0  # rt_readback_create formats (ABI 9, additive)
+RT_READBACK_BGRX = 1
 RT_TEXTURE_2D = 1
 RT_FORMAT_R8G8B8A8_UINT = 3
 
@@ -119,6 +121,13 @@ SIGNATURES = {
     "rt_recorder_write": (_i, [_vp, _vp, _i]),
     "rt_recorder_info": (_i, [_vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
     "rt_recorder_destroy": (None, [_vp]),
+    "rt_recorder_set_async": (_i, [_vp, _i]),
+    "rt_readback_create": (_i, [_vp, _i, _i, C.POINTER(_vp)]),
+    "rt_readback_submit": (_i, [_vp, C.POINTER(C.c_ulonglong)]),
+    "rt_readback_ready": (_i, [_vp, C.c_ulonglong]),
+    "rt_readback_wait": (_i, [_vp, C.c_ulonglong, C.POINTER(_vp)]),
+    "rt_readback_release": (_i, [_vp, C.c_ulonglong]),
+    "rt_readback_destroy": (None, [_vp]),
     "rt_varmgr_start": (_i, [_i, _cp]),
     "rt_varmgr_stop": (_i, []),
     "rt_varmgr_count": (_i, []),

@@ -151,6 +151,9 @@ inline size_t rt_shard_tiles(int w, int h, int rank, int count)
 }
 // RGBA8 framebuffer -> BGRX rows (RecorderWinAPI::write's swizzle), dst pitch in uint32 words
 void rt_launch_bgrx(hipStream_t s, const uint32_t* fb, uint32_t* dst, int w, int h, int pitch_words);
+// The readback ring's snapshot: `words` RGBA8 words of a framebuffer into a tight staging slot (both 16-byte
+// aligned), converted to BGRX on the way if bgrx != 0.  words < 2^32.
+void rt_launch_snapshot(hipStream_t s, const uint32_t* fb, uint32_t* dst, size_t words, int bgrx);
 // Shard transport jobs of one launch (a kernel argument: 2.5 KiB): job j copies shard shard[j]
 // of the w x h framebuffer fb[j] to packed[j] (pack != 0: 1024 px per tile, tiles ascending) or back.
 #define RT_SHARD_JOBS 128

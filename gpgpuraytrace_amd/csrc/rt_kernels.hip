@@ -2272,6 +2272,32 @@ __global__ void __launch_bounds__(256) k_bgrx(const uint32_t* __restrict__ fb, u
     }
 }
 
+// The readback ring's frame snapshot (rt_readback_submit): the W*H RGBA8 words of a framebuffer into a tightly
+// packed device staging slot, so that the next trace may overwrite the framebuffer while the slot's copy to the
+// host is still running.  Both buffers are one 1-D array (hipMalloc'd, so 16-byte aligned; tight rows): 16 B per
+// thread, the grid sized to the work, and the thread after the last quad copies the W*H mod 4 tail words.  BGRX:
+// RecorderWinAPI::write's conversion on the way (k_bgrx's selector).  A pure HBM stream (read and write W*H*4 B).
+template <bool BGRX>
+__global__ void __launch_bounds__(256) k_snapshot(const uint32_t* __restrict__ fb, uint32_t* __restrict__ dst,
+                                                  uint32_t words)
+{
+    constexpr uint32_t sel = 0x0c000102u; // (B, G, R, 0) from (R, G, B, A)
+    const uint32_t quads = words >> 2;
+    const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+    if (q < quads) {
+        uint4 v = reinterpret_cast<const uint4*>(fb)[q];
+        if (BGRX) {
+            v.x = __builtin_amdgcn_perm(0u, v.x, sel);
+            v.y = __builtin_amdgcn_perm(0u, v.y, sel);
+            v.z = __builtin_amdgcn_perm(0u, v.z, sel);
+            v.w = __builtin_amdgcn_perm(0u, v.w, sel);
+        }
+        reinterpret_cast<uint4*>(dst)[q] = v;
+    } else if (q == quads) {
+        for (uint32_t i = quads << 2; i < words; ++i) dst[i] = BGRX ? __builtin_amdgcn_perm(0u, fb[i], sel) : fb[i];
+    }
+}
+
 // Shard transport: job blockIdx.y copies tile blockIdx.x of its shard (tile blockIdx.x * count +
 // shard, row-major) between its framebuffer and its packed buffer (1024 RGBA8 pixels per tile,
 // row-major in the tile).  Thread t moves pixels 4 (t & 7) .. +3 of tile row t >> 3: one 16-byte
@@ -2442,6 +2468,16 @@ void rt_launch_bgrx(hipStream_t s, const uint32_t* fb, uint32_t* dst, int w, int
     const int quads = (w + 3) / 4;
     const int bx = (quads + 255) / 256;
     hipLaunchKernelGGL(k_bgrx, dim3(bx, h), dim3(256), 0, s, fb, dst, w, h, pitch_words);
+}
+
+void rt_launch_snapshot(hipStream_t s, const uint32_t* fb, uint32_t* dst, size_t words, int bgrx)
+{
+    if (words == 0 || words > 0xffffffffull) return; // (rt_readback_create rejects such a device)
+    const uint32_t n = (uint32_t)words;
+    const uint32_t threads = (n >> 2) + ((n & 3u) ? 1u : 0u); // one per quad, one more for the tail words
+    const uint32_t blocks = (threads + 255u) / 256u;
+    if (bgrx) hipLaunchKernelGGL(k_snapshot<true>, dim3(blocks), dim3(256), 0, s, fb, dst, n);
+    else hipLaunchKernelGGL(k_snapshot<false>, dim3(blocks), dim3(256), 0, s, fb, dst, n);
 }
 
 void rt_launch_shard_copy(hipStream_t s, const ShardJobs& jobs, int n, int w, int h, int count, int pack)

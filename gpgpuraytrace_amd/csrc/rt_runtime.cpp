@@ -32,6 +32,7 @@
 #include "rt_kernels.h"
 #include "rt_math.h"
 #include "rt_noise.h"
+#include "rt_ring.h"
 
 // RT_DEVICE_DEFERRED with one frame to a launch: frames of fewer pixels render as without the flag (at 256x256 the
 // fused prepass outlasts the frame's trace: 0.642 against 0.585 ms a frame; neutral at 1280x720)
@@ -233,6 +234,7 @@ struct rt_device_s {
     // output path: BGRX staging for the recorder / rt_device_readback_bgrx (allocated on first use)
     uint32_t* bgrx = nullptr;
     struct rt_recorder_s* recorder = nullptr; // DeviceDirect3D::recorder (setRecorder), not owned
+    std::vector<struct rt_readback_s*> rings; // readback rings on this device (rt_readback_create), not owned
     // children (IDevice::createCompute / createTexture); destroyed with the device
     std::vector<struct rt_compute_s*> computes;
     std::vector<struct rt_texture_s*> textures;
@@ -240,8 +242,84 @@ struct rt_device_s {
 };
 
 static int recorder_capture(rt_recorder r);
+static int recorder_capture_async(rt_recorder r);
+static bool recorder_is_async(rt_recorder r);
 static void recorder_detach(rt_recorder r);
 static int defer_flush(rt_device d);
+
+// ---------------------------------------------------------------------------
+// The readback ring (rt_readback_*): `depth` device staging slots, as many pinned host slots, one copy stream
+// and two events per slot, all made by rt_readback_create.  A submit snapshots the frame into a staging slot on
+// the device stream (k_snapshot), and the copy stream carries it to the pinned slot behind an event, so no call
+// but rt_readback_wait waits for the GPU and the device stream carries nothing but the snapshot.  rt_ring.h
+// keeps the tickets and slot states.
+struct rt_readback_s {
+    rt_device dev = nullptr; // nullptr once the device is gone (ring_detach)
+    int ordinal = 0, format = 0;
+    size_t words = 0;
+    RtRing ring;
+    uint32_t* stage[RtRing::MAX_DEPTH] = {};
+    void* host[RtRing::MAX_DEPTH] = {};
+    hipEvent_t ev_snap[RtRing::MAX_DEPTH] = {}, ev_done[RtRing::MAX_DEPTH] = {};
+    // an ATTACHED capture's frame: RING_FRAME_DEFER = the device's pending frame (d->defer), else its frame slot
+    int frame[RtRing::MAX_DEPTH] = {};
+    float frame_time[RtRing::MAX_DEPTH] = {}; // the recorder's time stamp input of the capture (set_async)
+    hipStream_t copy = nullptr;
+    explicit rt_readback_s(int depth) : ring(depth) {}
+    ~rt_readback_s()
+    {
+        (void)hipSetDevice(ordinal);
+        if (copy) {
+            (void)hipStreamSynchronize(copy); // the copies in flight write the pinned slots freed below
+            (void)hipStreamDestroy(copy);
+        }
+        for (int i = 0; i < RtRing::MAX_DEPTH; ++i) {
+            if (ev_snap[i]) (void)hipEventDestroy(ev_snap[i]);
+            if (ev_done[i]) (void)hipEventDestroy(ev_done[i]);
+            if (stage[i]) (void)hipFree(stage[i]);
+            if (host[i]) (void)hipHostFree(host[i]);
+        }
+    }
+};
+enum { RING_FRAME_DEFER = -1, RING_FRAME_ALL = -2 };
+
+// queue ring slot `slot`'s capture of the framebuffer `src` behind what the device stream holds
+static int ring_enqueue(rt_readback_s* rb, int slot, const uint32_t* src)
+{
+    hipStream_t s = rb->dev->stream;
+    auto queue = [&]() -> int {
+        rt_launch_snapshot(s, src, rb->stage[slot], rb->words, rb->format == RT_READBACK_BGRX);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(rb->ev_snap[slot], s));
+        HIP_TRY(hipStreamWaitEvent(rb->copy, rb->ev_snap[slot], 0));
+        HIP_TRY(hipMemcpyAsync(rb->host[slot], rb->stage[slot], rb->words * 4, hipMemcpyDeviceToHost, rb->copy));
+        HIP_TRY(hipEventRecord(rb->ev_done[slot], rb->copy));
+        return RT_OK;
+    };
+    const int rc = queue();
+    if (rc) (void)hipStreamSynchronize(rb->copy); // whatever part was queued is over before the slot is reused
+    return rc;
+}
+
+// The trace of frame `frame` of device d was just launched into `src` (rc == RT_OK), or the frame was dropped on
+// a launch error (rc != RT_OK): the captures attached to it are queued right behind it, or failed.
+static void captures_launch(rt_device d, int frame, const uint32_t* src, int rc)
+{
+    for (rt_readback_s* rb : d->rings)
+        for (int s = 0; s < rb->ring.depth(); ++s) {
+            if (rb->ring.state(s) != RtRing::ATTACHED || (frame != RING_FRAME_ALL && rb->frame[s] != frame)) continue;
+            if (rc == RT_OK && ring_enqueue(rb, s, src) == RT_OK) rb->ring.launched(s);
+            else rb->ring.fail(s);
+        }
+}
+
+// the device goes away: its rings keep their buffers, every capture not handed out fails
+static void ring_detach(rt_readback_s* rb)
+{
+    rb->ring.cancel();
+    rb->dev = nullptr;
+}
+static int recorder_drain(rt_recorder r);
 
 namespace {
 // Work on stream s that touches device d's frames (their CameraResults) comes after a pending ahead
@@ -801,6 +879,7 @@ rt_device_s::~rt_device_s()
                     (void*)bgrx, (void*)table.d, (void*)pre_table.d, (void*)fuse_table.d, (void*)fctl, (void*)blocks})
         if (p) (void)hipFree(p);
     if (recorder) recorder_detach(recorder); // the recorder outlives its device: it stops capturing
+    for (rt_readback_s* rb : rings) ring_detach(rb); // so do its rings: later calls return RT_ERR_STATE
     if (graph_pre.exec) (void)hipGraphExecDestroy(graph_pre.exec);
     if (graph_trace.exec) (void)hipGraphExecDestroy(graph_trace.exec);
     for (hipEvent_t e : {sync_ev, ev_order, ev_ahead, ev_ahead_in, ev_fuser_done, ev_fuse_order, ev_pre})
@@ -858,6 +937,7 @@ int rt_device_create(int ordinal, int width, int height, unsigned flags, rt_devi
 void rt_device_destroy(rt_device d)
 {
     if (d) (void)defer_flush(d); // a pending frame is traced (the destructor then drains the stream)
+    if (d && d->recorder) (void)recorder_drain(d->recorder); // an asynchronous recorder writes what it captured
     delete d;
 }
 
@@ -875,6 +955,7 @@ int rt_device_present(rt_device d)
     if (int rc = host_flag_check(d)) return rc;
     // DeviceDirect3D.cpp:242-256: while recording, the frame goes to the recorder
     if (d->recorder && rt_recorder_is_recording(d->recorder) == 1) {
+        if (recorder_is_async(d->recorder)) return recorder_capture_async(d->recorder); // (launches no pending frame)
         if (int rc = defer_flush(d)) return rc;
         return recorder_capture(d->recorder);
     }
@@ -1870,7 +1951,9 @@ static int defer_flush_one(rt_device d)
     if (!d->defer.pending) return RT_OK;
     const rt_device_s::Deferred p = d->defer;
     d->defer.pending = false;
-    return terrain_render_batch(&p.cam, &p.scr, 1, p.rank, p.count, false, PH_TRACE | PH_KEEP);
+    const int rc = terrain_render_batch(&p.cam, &p.scr, 1, p.rank, p.count, false, PH_TRACE | PH_KEEP);
+    captures_launch(d, RING_FRAME_DEFER, d->fb8, rc); // the frame's captures right behind its trace
+    return rc;
 }
 
 static int defer_flush(rt_device d)
@@ -1938,9 +2021,10 @@ static int deferred_render(rt_device d, rt_compute cam, rt_compute scr, int shar
         TraceFuse tf;
         tf.next = FusedPrepass{d->fuse_table.d, d->fctl, (uint32_t)RT_FUSE_TASKS_PER_FRAME};
         d->defer.pending = false;
-        if (int rc = terrain_render_batch(&p.cam, &p.scr, 1, p.rank, p.count, false, PH_TRACE | PH_KEEP, 0, -1,
-                                          nullptr, nullptr, &tf))
-            return rc;
+        const int rc = terrain_render_batch(&p.cam, &p.scr, 1, p.rank, p.count, false, PH_TRACE | PH_KEEP, 0, -1,
+                                            nullptr, nullptr, &tf);
+        captures_launch(d, RING_FRAME_DEFER, d->fb8, rc); // the pending frame's captures right behind its trace
+        if (rc) return rc;
         ++d->deferred_fused;
     }
     // this frame's tracescreen constants (and noise gradients), behind the trace that read the previous frame's
@@ -2036,6 +2120,7 @@ static int batch_trace(rt_device d, int n, int m, bool last)
             HIP_TRY(hipMemcpyAsync(cr->dev_ptr, ft.cam[n - 1], 1024 * sizeof(float4), hipMemcpyDeviceToDevice, d->stream));
     }
     HIP_TRY(hipGetLastError());
+    for (int i = 0; i < n; ++i) captures_launch(d, d->dq[i], ft.out8[i], RT_OK); // from the buffer frame i wrote
     for (int i = 0; i < n; ++i) d->dq.pop_front();
     d->dq_pre = m;
     return RT_OK;
@@ -2068,6 +2153,7 @@ static int defer_flush_batch(rt_device d)
             if (int rc = batch_prepass(d, std::min<int>(K, (int)d->dq.size()))) return rc;
         const int n = d->dq_pre, m = std::min<int>(K, (int)d->dq.size() - n);
         if (int rc = batch_trace(d, n, m, (int)d->dq.size() == n)) {
+            captures_launch(d, RING_FRAME_ALL, nullptr, rc); // the queued frames are dropped: their captures fail
             d->dq.clear();
             d->dq_pre = 0;
             return rc;
@@ -2515,6 +2601,123 @@ extern "C" int rt_debug_sky(rt_compute c, const float* dirs, float* out, int n)
 }
 
 // ---------------------------------------------------------------------------
+// rt_readback_*: the asynchronous readback ring (struct rt_readback_s above; include/frosttrace.h)
+int rt_readback_create(rt_device d, int format, int depth, rt_readback* out)
+{
+    if (!out) return fail(RT_ERR_INVALID, "bad readback ring arguments");
+    *out = nullptr;
+    if (format != RT_READBACK_RGBA8 && format != RT_READBACK_BGRX) return fail(RT_ERR_INVALID, "unknown readback format %d", format);
+    if (depth < 1 || depth > RtRing::MAX_DEPTH) return fail(RT_ERR_INVALID, "a readback ring holds 1..%d captures, not %d", (int)RtRing::MAX_DEPTH, depth);
+    if (!d) return fail(RT_ERR_INVALID, "null device");
+    const size_t words = (size_t)d->width * (size_t)d->height;
+    if (words > 0xffffffffull) return fail(RT_ERR_UNSUPPORTED, "readback ring: frames of fewer than 2^32 pixels");
+    HIP_TRY(hipSetDevice(d->ordinal));
+    // from here on every early return frees what was made (the destructor)
+    auto rb = std::make_unique<rt_readback_s>(depth);
+    rb->ordinal = d->ordinal;
+    rb->format = format;
+    rb->words = words;
+    HIP_TRY(hipStreamCreateWithFlags(&rb->copy, hipStreamNonBlocking));
+    for (int i = 0; i < depth; ++i) {
+        HIP_TRY(hipMalloc(&rb->stage[i], words * 4));
+        HIP_TRY(hipHostMalloc(&rb->host[i], words * 4));
+        HIP_TRY(hipEventCreateWithFlags(&rb->ev_snap[i], hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&rb->ev_done[i], hipEventDisableTiming));
+    }
+    rb->dev = d;
+    d->rings.push_back(rb.get());
+    *out = rb.release();
+    return RT_OK;
+}
+
+int rt_readback_submit(rt_readback rb, unsigned long long* ticket)
+{
+    if (!rb || !ticket) return fail(RT_ERR_INVALID, "bad readback submit arguments");
+    rt_device d = rb->dev;
+    if (!d) return fail(RT_ERR_STATE, "readback ring: its device was destroyed");
+    HIP_TRY(hipSetDevice(d->ordinal));
+    if (int rc = host_flag_check(d)) return rc;
+    const int slot = rb->ring.peek();
+    if (slot < 0) return fail(RT_ERR_STATE, "readback ring full: release a capture first");
+    // the newest rendered frame: queued for a batch (K >= 2), pending (K = 1), or already launched
+    if (!d->dq.empty() || d->defer.pending) {
+        rb->frame[slot] = !d->dq.empty() ? d->dq.back() : (int)RING_FRAME_DEFER;
+        rb->ring.submit(RtRing::ATTACHED, ticket);
+        return RT_OK;
+    }
+    if (int rc = ring_enqueue(rb, slot, d->fb8)) return rc;
+    rb->ring.submit(RtRing::INFLIGHT, ticket);
+    return RT_OK;
+}
+
+// the live capture of a ticket on a ring that still has its device (RT_OK and *slot), or the error
+static int ring_lookup(rt_readback rb, unsigned long long ticket, int* slot)
+{
+    if (!rb) return fail(RT_ERR_INVALID, "null readback ring");
+    if (!rb->dev) return fail(RT_ERR_STATE, "readback ring: its device was destroyed");
+    *slot = rb->ring.find(ticket);
+    if (*slot < 0) return fail(RT_ERR_INVALID, "readback ring: ticket %llu is unknown or released", ticket);
+    return RT_OK;
+}
+
+int rt_readback_ready(rt_readback rb, unsigned long long ticket)
+{
+    int slot = -1;
+    if (int rc = ring_lookup(rb, ticket, &slot)) return rc;
+    switch (rb->ring.state(slot)) {
+    case RtRing::ATTACHED: return 0; // its frame is not launched (and this call launches nothing)
+    case RtRing::INFLIGHT: {
+        const hipError_t e = hipEventQuery(rb->ev_done[slot]);
+        if (e == hipErrorNotReady) return 0;
+        if (e != hipSuccess) return fail(RT_ERR_HIP, "hipEventQuery: %s", hipGetErrorString(e));
+        rb->ring.ready(slot);
+        return 1;
+    }
+    case RtRing::READY:
+    case RtRing::HELD: return 1;
+    default: return fail(RT_ERR_STATE, "readback ring: capture %llu failed (its frame was dropped)", ticket);
+    }
+}
+
+int rt_readback_wait(rt_readback rb, unsigned long long ticket, const void** pixels)
+{
+    if (pixels) *pixels = nullptr;
+    if (!rb || !pixels) return fail(RT_ERR_INVALID, "bad readback wait arguments");
+    int slot = -1;
+    if (int rc = ring_lookup(rb, ticket, &slot)) return rc;
+    rt_device d = rb->dev;
+    if (rb->ring.state(slot) == RtRing::ATTACHED) // not queued yet: its event would never fire
+        if (int rc = defer_flush(d)) return rc;
+    if (rb->ring.state(slot) == RtRing::ATTACHED) return fail(RT_ERR_STATE, "readback ring: capture %llu was never launched", ticket);
+    if (rb->ring.state(slot) == RtRing::FAILED) return fail(RT_ERR_STATE, "readback ring: capture %llu failed (its frame was dropped)", ticket);
+    if (rb->ring.state(slot) == RtRing::INFLIGHT) HIP_TRY(hipEventSynchronize(rb->ev_done[slot]));
+    // the fail-safe word after the sync, as recorder_capture: a possibly wrong frame is never handed out
+    if (int rc = host_flag_check(d)) {
+        if (rb->ring.state(slot) == RtRing::INFLIGHT) rb->ring.fail(slot); // (its copy is over: release may free it)
+        return rc;
+    }
+    rb->ring.hold(slot);
+    *pixels = rb->host[slot];
+    return RT_OK;
+}
+
+int rt_readback_release(rt_readback rb, unsigned long long ticket)
+{
+    int slot = -1;
+    if (int rc = ring_lookup(rb, ticket, &slot)) return rc;
+    if (!rb->ring.release(slot)) return fail(RT_ERR_STATE, "readback ring: capture %llu is still in flight (wait for it first)", ticket);
+    return RT_OK;
+}
+
+void rt_readback_destroy(rt_readback rb)
+{
+    if (!rb) return;
+    if (rt_device d = rb->dev) d->rings.erase(std::remove(d->rings.begin(), d->rings.end(), rb), d->rings.end());
+    rb->ring.cancel(); // attached captures are never queued; the destructor drains the copy stream
+    delete rb;
+}
+
+// ---------------------------------------------------------------------------
 // IRecorder / RecorderWinAPI (Factories/IRecorder.h, Adapters/RecorderWinAPI.cpp) over a
 // raw-video sink: Media Foundation's WMV sink writer does not exist here, so the frames
 // are appended as raw MFVideoFormat_RGB32 (B, G, R, 0) rows to `path` (ffmpeg reads it as
@@ -2533,8 +2736,10 @@ struct rt_recorder_s {
     uint64_t frames = 0;
     uint32_t* host = nullptr;                // pinned W*H*4 staging (swapStaging's role)
     std::vector<uint32_t> conv;              // CPU conversion buffer of rt_recorder_write (pBuffer's role)
+    rt_readback ring = nullptr;              // rt_recorder_set_async: its BGRX readback ring (owned)
     ~rt_recorder_s()
     {
+        rt_readback_destroy(ring);
         if (video) fclose(video);
         if (index) fclose(index);
         if (host) (void)hipHostFree(host);
@@ -2544,12 +2749,12 @@ struct rt_recorder_s {
 
 static void recorder_detach(rt_recorder r) { r->dev = nullptr; }
 
-static int recorder_sample(rt_recorder r, const uint32_t* bgrx)
+static int recorder_sample(rt_recorder r, const uint32_t* bgrx, float frame_time)
 {
     // RecorderWinAPI.cpp:264-274: fixed speed = 1/frameRate per frame, else the frame's
     // own time in float (10000000.0f * modifier, truncated)
     uint64_t dur = r->rt_duration;
-    if (!r->fixed_speed) dur = (uint64_t)(10000000.0f * r->frame_time);
+    if (!r->fixed_speed) dur = (uint64_t)(10000000.0f * frame_time);
     const size_t n = (size_t)r->width * r->height;
     if (fwrite(bgrx, 4, n, r->video) != n) return fail(RT_ERR_STATE, "recorder: short write to %s", r->path.c_str());
     fprintf(r->index, "%llu %llu %llu\n", (unsigned long long)r->frames, (unsigned long long)r->rt_start,
@@ -2569,7 +2774,72 @@ static int recorder_capture(rt_recorder r)
     // the fail-safe word after the sync: a fused-prepass timeout raised by this frame's own k_order
     // (asynchronous to rt_device_present's check) keeps the possibly wrong frame out of the video
     if (int rc = host_flag_check(d)) return rc;
-    return recorder_sample(r, r->host);
+    return recorder_sample(r, r->host, r->frame_time);
+}
+
+// ---- the pipelined recorder (rt_recorder_set_async) ----
+static bool recorder_is_async(rt_recorder r) { return r->ring != nullptr; }
+
+// wait for the oldest capture, write its sample and free its slot; a capture whose wait fails writes none
+static int recorder_drain_one(rt_recorder r)
+{
+    rt_readback rb = r->ring;
+    const int slot = rb->ring.oldest();
+    if (slot < 0) return RT_OK;
+    const void* px = nullptr;
+    int rc = rb->dev ? rt_readback_wait(rb, rb->ring.ticket(slot), &px)
+                     : fail(RT_ERR_STATE, "recorder: the device was destroyed with a capture in flight");
+    if (rc == RT_OK) rc = recorder_sample(r, static_cast<const uint32_t*>(px), rb->frame_time[slot]);
+    rb->ring.fail(slot); // (a wait that failed on a HIP error leaves it in flight; a held or failed one stays so)
+    rb->ring.release(slot);
+    return rc;
+}
+
+// write everything captured; the first error is returned, after the rest was drained
+static int recorder_drain(rt_recorder r)
+{
+    int first = RT_OK;
+    std::string msg;
+    while (r->ring && r->ring->ring.live() > 0)
+        if (int rc = recorder_drain_one(r))
+            if (first == RT_OK) {
+                first = rc;
+                msg = g_err;
+            }
+    if (first != RT_OK) g_err = msg;
+    return first;
+}
+
+static int recorder_capture_async(rt_recorder r)
+{
+    if (!r->begun || r->finalized) return fail(RT_ERR_STATE, "recorder: write outside BeginWriting/Finalize");
+    rt_readback rb = r->ring;
+    if (rb->ring.peek() < 0) // ring full: block on the oldest capture and write it
+        if (int rc = recorder_drain_one(r)) return rc;
+    const int slot = rb->ring.peek();
+    unsigned long long t = 0;
+    if (int rc = rt_readback_submit(rb, &t)) return rc;
+    rb->frame_time[slot] = r->frame_time; // Timer::getConstant() of this frame, used when its sample is written
+    // the older captures that are ready, in order
+    for (int o = rb->ring.oldest(); o >= 0 && rb->ring.ticket(o) != t; o = rb->ring.oldest()) {
+        const int rdy = rt_readback_ready(rb, rb->ring.ticket(o));
+        if (rdy == 0) break;
+        if (int rc = recorder_drain_one(r)) return rc; // (a failed capture surfaces here)
+    }
+    return RT_OK;
+}
+
+int rt_recorder_set_async(rt_recorder r, int depth)
+{
+    if (!r) return fail(RT_ERR_INVALID, "null recorder");
+    if (depth < 0 || depth > RtRing::MAX_DEPTH) return fail(RT_ERR_INVALID, "recorder: asynchronous depth 0..%d, not %d", (int)RtRing::MAX_DEPTH, depth);
+    const int drained = recorder_drain(r);
+    rt_readback_destroy(r->ring);
+    r->ring = nullptr;
+    if (drained) return drained;
+    if (depth == 0) return RT_OK;
+    if (!r->dev) return fail(RT_ERR_STATE, "recorder: its device was destroyed");
+    return rt_readback_create(r->dev, RT_READBACK_BGRX, depth, &r->ring);
 }
 
 int rt_recorder_create(rt_device d, int frame_rate, int fixed_speed, const char* path, rt_recorder* out)
@@ -2616,7 +2886,9 @@ int rt_recorder_stop(rt_recorder r)
     if (!r) return fail(RT_ERR_INVALID, "null recorder");
     r->recording = false; // IRecorder::stop, then Finalize
     if (!r->begun || r->finalized) return RT_OK;
+    const int drained = recorder_drain(r); // an asynchronous recorder's captures in flight are written first
     r->finalized = true;
+    if (drained) return drained;
     if (fflush(r->video) != 0 || fflush(r->index) != 0) return fail(RT_ERR_STATE, "recorder: flush failed");
     return RT_OK;
 }
@@ -2634,6 +2906,7 @@ int rt_recorder_write(rt_recorder r, const void* frame, int stride)
 {
     if (!r || !frame || stride < r->width * 4) return fail(RT_ERR_INVALID, "bad recorder write arguments");
     if (!r->begun || r->finalized) return fail(RT_ERR_STATE, "recorder: write outside BeginWriting/Finalize");
+    if (int rc = recorder_drain(r)) return rc; // (samples stay in order behind an asynchronous recorder's captures)
     // RecorderWinAPI.cpp:244-253 on host memory, as the interface receives it
     r->conv.resize((size_t)r->width * r->height);
     for (int y = 0; y < r->height; ++y) {
@@ -2644,13 +2917,14 @@ int rt_recorder_write(rt_recorder r, const void* frame, int stride)
             o[x] = (dwc & 0x0000FF00u) | (dwc & 0x000000FFu) << 16 | (dwc & 0x00FF0000u) >> 16;
         }
     }
-    return recorder_sample(r, r->conv.data());
+    return recorder_sample(r, r->conv.data(), r->frame_time);
 }
 
 int rt_recorder_info(rt_recorder r, unsigned long long* frames, unsigned long long* next_sample_time,
                      unsigned long long* frame_duration)
 {
     if (!r) return fail(RT_ERR_INVALID, "null recorder");
+    if (int rc = recorder_drain(r)) return rc;
     if (frames) *frames = r->frames;
     if (next_sample_time) *next_sample_time = r->rt_start;
     if (frame_duration) *frame_duration = r->rt_duration;

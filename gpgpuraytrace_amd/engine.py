@@ -224,6 +224,11 @@ class Device:
         check(lib().rt_device_readback_bgrx(self._h, out.ctypes.data, self.width * 4), "readback_bgrx")
         return out
 
+    def readback_ring(self, format="rgba8", depth=3):
+        """rt_readback_create (ABI 9, additive): a ring of `depth` (1..8) asynchronous captures of this device's
+        frames, "rgba8" (readback()'s bytes) or "bgrx" (readback_bgrx()'s)."""
+        return ReadbackRing(self, format, depth)
+
     def stats(self, reset=True):
         s = _native.RtStats()
         check(lib().rt_device_stats_sized(self._h, C.byref(s), C.sizeof(s), 1 if reset else 0), "stats")
@@ -298,6 +303,54 @@ class Device:
             self._h = None
 
 
+class ReadbackRing:
+    """rt_readback_* (ABI 9, additive): frames handed to the host without a host synchronisation per frame.
+    submit() captures the latest render's frame and returns its ticket without waiting for the GPU (on a
+    deferred device without launching the pending frame); wait(t) returns the capture's pinned slot as a
+    read-only array, valid until release(t)."""
+
+    FORMATS = {"rgba8": _native.RT_READBACK_RGBA8, "bgrx": _native.RT_READBACK_BGRX}
+
+    def __init__(self, device, format="rgba8", depth=3):
+        if format not in self.FORMATS:
+            raise ValueError(f"readback ring format {format!r}: 'rgba8' or 'bgrx'")
+        self.device, self.format, self.depth = device, format, int(depth)
+        h = C.c_void_p()
+        check(lib().rt_readback_create(device._h, self.FORMATS[format], self.depth, C.byref(h)), "readback ring")
+        self._h = h.value
+
+    def submit(self):
+        t = C.c_ulonglong()
+        check(lib().rt_readback_submit(self._h, C.byref(t)), "readback submit")
+        return int(t.value)
+
+    def ready(self, ticket):
+        """True once the capture is in its pinned slot; launches nothing."""
+        rc = lib().rt_readback_ready(self._h, int(ticket))
+        if rc < 0:
+            check(rc, "readback ready")
+        return rc == 1
+
+    def wait(self, ticket):
+        """(H, W, 4) uint8 ("rgba8") or (H, W) uint32 ("bgrx"): a read-only view of the pinned slot."""
+        p = C.c_void_p()
+        check(lib().rt_readback_wait(self._h, int(ticket), C.byref(p)), "readback wait")
+        w, h = self.device.width, self.device.height
+        buf = (C.c_ubyte * (w * h * 4)).from_address(p.value)
+        a = np.frombuffer(buf, np.uint8).reshape(h, w, 4) if self.format == "rgba8" else \
+            np.frombuffer(buf, np.uint32).reshape(h, w)
+        a.flags.writeable = False
+        return a
+
+    def release(self, ticket):
+        check(lib().rt_readback_release(self._h, int(ticket)), "readback release")
+
+    def destroy(self):
+        if self._h:
+            lib().rt_readback_destroy(self._h)
+            self._h = None
+
+
 class DeviceFactory:
     @staticmethod
     def construct(api, width, height, gpu=0, **kw):
@@ -335,6 +388,12 @@ class Recorder:
         a = np.ascontiguousarray(frame)
         check(lib().rt_recorder_write(self._h, a.ctypes.data, int(stride or a.strides[0])), "recorder write")
 
+    def set_async(self, depth):
+        """rt_recorder_set_async (ABI 9, additive): depth 1..8 = a recording present() submits the frame to a BGRX
+        readback ring and writes the older frames that are ready, instead of waiting for the frame; 0 = synchronous
+        (the default).  stop(), info(), destroy() and this call write everything captured first; same files."""
+        check(lib().rt_recorder_set_async(self._h, int(depth)), "recorder set_async")
+
     def info(self):
         f, t, d = C.c_ulonglong(), C.c_ulonglong(), C.c_ulonglong()
         check(lib().rt_recorder_info(self._h, C.byref(f), C.byref(t), C.byref(d)), "recorder info")
@@ -348,10 +407,14 @@ class Recorder:
 
 class RecorderFactory:
     @staticmethod
-    def construct(device, frame_rate, fixed_speed, path="output.rgb32"):
-        """RecorderFactory::construct (RecorderFactory.cpp:6-19): None on failure."""
+    def construct(device, frame_rate, fixed_speed, path="output.rgb32", async_depth=0):
+        """RecorderFactory::construct (RecorderFactory.cpp:6-19): None on failure.  async_depth > 0: the
+        pipelined recorder (Recorder.set_async)."""
         h = C.c_void_p()
         if lib().rt_recorder_create(device._h, int(frame_rate), 1 if fixed_speed else 0, path.encode(), C.byref(h)):
+            return None
+        if async_depth and lib().rt_recorder_set_async(h.value, int(async_depth)):
+            lib().rt_recorder_destroy(h.value)
             return None
         return Recorder(h.value, device, path)
 

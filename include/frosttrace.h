@@ -83,7 +83,7 @@ enum {
  * dispatches until the next submission, without a prepass launch that waits for the trace's CUs.  Every other
  * call that launches on, reads, waits on or reconfigures the device -- rt_device_flush, _synchronize,
  * _readback*, _stats*, _kernel_time, _set_stream, _wait_event, _record_event, _check, _framebuffer, _stream,
- * _destroy, rt_device_present while recording, any other render, prepass or shard call, a map / unmap / write
+ * _destroy, rt_device_present while recording (synchronously; not with rt_recorder_set_async), any other render, prepass or shard call, a map / unmap / write
  * or device pointer of its arrays, a compute run / swap / destroy / set_texture, a texture init / destroy,
  * rt_device_defer_batch -- launches a pending
  * frame first.  rt_device_present without a recorder launches nothing (there is no display): a caller that
@@ -214,6 +214,52 @@ int rt_device_record_event(rt_device dev, void* hip_event);
  * that GPU reports and clears it.  A host that follows the reference's call sequence and never calls
  * rt_device_check therefore cannot read such a frame silently. */
 int rt_device_check(rt_device dev);
+
+/* ---- Asynchronous frame readback (ABI 9, additive) ----
+ * rt_device_readback* and a recording rt_device_present end in a host synchronisation, so a host that looks at
+ * every frame (a window blit, the recorder, the reference's render / present / readback loop) never has a frame
+ * in flight.  A readback ring hands frames to the host without one.  No reference counterpart (the reference
+ * maps its staging texture in present(), DeviceDirect3D.cpp:244-256).
+ * rt_readback_create  (ABI 9, additive) a ring of `depth` (1..8) captures of `dev`'s frames, RT_READBACK_RGBA8
+ *                     (rt_device_readback's bytes) or RT_READBACK_BGRX (rt_device_readback_bgrx's).  It owns
+ *                     `depth` device staging slots, `depth` pinned host slots (W*H*4 bytes, tight rows), one
+ *                     non-blocking copy stream and two events per slot (timing disabled), all made here: no call
+ *                     below allocates.  An allocation failure frees what was made and returns the error.
+ * rt_readback_submit  (ABI 9, additive) captures the frame rt_device_readback would return if called now -- the
+ *                     latest render's -- and returns its ticket (0, 1, 2, ...).  It never waits for the GPU: a
+ *                     snapshot kernel copies the framebuffer into a staging slot on the device stream (so the
+ *                     next trace may overwrite the framebuffer), and the copy stream carries the slot to pinned
+ *                     memory behind an event.  Only the framebuffer is touched: the frames-in-flight path of
+ *                     rt_terrain_render goes on (the next prepass still runs on the prepass stream), and an
+ *                     RT_DEVICE_GRAPH device re-captures nothing.  With every slot still the caller's it returns
+ *                     RT_ERR_STATE ("ring full") and queues nothing.  On an RT_DEVICE_DEFERRED device it does NOT
+ *                     launch a pending frame: the capture is attached to the newest rendered frame and queued
+ *                     right behind that frame's trace by whichever call launches it, from the buffer the frame
+ *                     really wrote; with nothing pending it is queued at once.  A capture whose frame is dropped
+ *                     on a launch error fails (wait and ready return RT_ERR_STATE; release frees it).  At K frames
+ *                     to a launch (rt_device_defer_batch) a frame's trace goes out up to 2K-1 renders after its
+ *                     own, so a consumer that waits for a newer ticket than n-(2K-1) launches the queue early,
+ *                     and one that lags fewer than 2K+1 frames leaves the GPU nothing queued while it waits
+ *                     (a ring of 2K+2 keeps K = 2 at its rate, profiles/r07/readback_ring.md).
+ * rt_readback_ready   (ABI 9, additive) 1 = the capture is in its pinned slot, 0 = not yet (always, while its
+ *                     frame is not launched), < 0 = error.  Launches nothing.
+ * rt_readback_wait    (ABI 9, additive) launches what is pending if the capture is not queued yet, waits for that
+ *                     capture's event only (not the stream), then checks the fail-safe word (rt_device_check):
+ *                     if it is set, RT_ERR_STATE, *pixels = NULL and the capture has failed; else *pixels is the
+ *                     pinned slot, valid until rt_readback_release.  Waiting twice is allowed.
+ * rt_readback_release (ABI 9, additive) returns a capture's slot to the ring after a successful wait, a ready
+ *                     result of 1, or a failure; in any order.  RT_ERR_STATE for a capture still in flight.
+ * An unknown or released ticket is RT_ERR_INVALID everywhere.
+ * rt_readback_destroy (ABI 9, additive) drains the copy stream and cancels attached captures.  rt_device_destroy
+ *                     before it detaches the ring (as a recorder): every later call returns RT_ERR_STATE. */
+enum { RT_READBACK_RGBA8 = 0, RT_READBACK_BGRX = 1 };
+typedef struct rt_readback_s* rt_readback;
+int rt_readback_create(rt_device dev, int format, int depth, rt_readback* out);
+int rt_readback_submit(rt_readback rb, unsigned long long* ticket);
+int rt_readback_ready(rt_readback rb, unsigned long long ticket);
+int rt_readback_wait(rt_readback rb, unsigned long long ticket, const void** pixels);
+int rt_readback_release(rt_readback rb, unsigned long long ticket);
+void rt_readback_destroy(rt_readback rb);
 
 /* ---- ITexture (IDevice::createTexture + ITexture::create(dims, fmt, w, h, data, binding, cpu)) ---- */
 int rt_texture_create(rt_device dev, rt_texture* out);
@@ -407,6 +453,15 @@ int rt_recorder_write(rt_recorder rec, const void* frame, int stride);
 int rt_recorder_info(rt_recorder rec, unsigned long long* frames, unsigned long long* next_sample_time,
                      unsigned long long* frame_duration);
 void rt_recorder_destroy(rt_recorder rec);
+/* rt_recorder_set_async (ABI 9, additive; no reference counterpart): depth 1..8 gives the recorder a BGRX readback
+ * ring of its own, 0 (the default) takes it away.  With a ring a recording rt_device_present submits a capture
+ * instead of waiting for the frame (on an RT_DEVICE_DEFERRED device it launches nothing), keeps the frame's time
+ * stamp input (rt_recorder_set_frame_time) with it, then writes the samples of the older captures that are ready,
+ * in order; with the ring full it first waits for the oldest and writes it.  rt_recorder_stop, _info, _destroy,
+ * this call and rt_device_destroy write everything captured first, so `frames` always counts the recording
+ * presents, and `path` and `path`.txt hold the synchronous recorder's bytes.  A capture whose wait fails (the
+ * fail-safe word) writes no sample; the call that drained it returns the error.  No writer thread. */
+int rt_recorder_set_async(rt_recorder rec, int depth);
 
 /* ---- VariableManager (Common/VariableManager.{h,cpp}; main.cpp:99 `-m`) ----
  * The live-tweak TCP protocol (VariableManager.cpp:76-83): on connect the server sends every

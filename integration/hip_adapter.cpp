@@ -78,7 +78,11 @@ void ComputeHIP::setTexture(int stage, ITexture* texture)
 }
 
 DeviceHIP::DeviceHIP(IWindow* window) : IDevice(kDeviceApiHip, window) { }
-DeviceHIP::~DeviceHIP() { rt_device_destroy(dev); }
+DeviceHIP::~DeviceHIP()
+{
+    rt_readback_destroy(ring);
+    rt_device_destroy(dev);
+}
 
 bool DeviceHIP::create()
 {
@@ -97,6 +101,20 @@ ICompute* DeviceHIP::createCompute() { return new ComputeHIP(dev); }
 ITexture* DeviceHIP::createTexture() { return new TextureHIP(dev); }
 
 bool DeviceHIP::readback(void* dst, size_t rowPitch) const { return rt_device_readback(dev, dst, rowPitch) == RT_OK; }
+
+bool DeviceHIP::readbackSubmit(unsigned long long* ticket)
+{
+    if (!ring && rt_readback_create(dev, RT_READBACK_RGBA8, 3, &ring) != RT_OK) return false;
+    return rt_readback_submit(ring, ticket) == RT_OK;
+}
+
+const void* DeviceHIP::readbackWait(unsigned long long ticket)
+{
+    const void* pixels = nullptr;
+    return ring && rt_readback_wait(ring, ticket, &pixels) == RT_OK ? pixels : nullptr;
+}
+
+bool DeviceHIP::readbackRelease(unsigned long long ticket) { return ring && rt_readback_release(ring, ticket) == RT_OK; }
 
 bool RecorderHIP::create()
 {

@@ -98,6 +98,13 @@ public:
     ICompute* createCompute() override;
     ITexture* createTexture() override;
     bool readback(void* dst, size_t rowPitch) const;
+    // (adapter extension) the frame without a host synchronisation per frame, over rt_readback_* (ABI 9, additive):
+    // readbackSubmit captures the frame readback() would return now and hands out its ticket (an RGBA8 ring of 3
+    // captures, made at the first submit); readbackWait returns its tight RGBA8 rows, valid until readbackRelease.
+    // The reference's present() maps its staging texture every frame (DeviceDirect3D.cpp:244-256).
+    bool readbackSubmit(unsigned long long* ticket);
+    const void* readbackWait(unsigned long long ticket);
+    bool readbackRelease(unsigned long long ticket);
     rt_device handle() const { return dev; }
     void setRecorder(class RecorderHIP* r) { recorder = r; } // DeviceDirect3D::setRecorder (:229-232)
     // (adapter extension, before create) rt_device_create's flags, e.g. RT_DEVICE_DEFERRED (ABI 9): the reference's
@@ -106,6 +113,7 @@ public:
 
 private:
     rt_device dev = nullptr;
+    rt_readback ring = nullptr;
     unsigned flags = 0;
     class RecorderHIP* recorder = nullptr;
 };
@@ -124,6 +132,9 @@ public:
     void start() override { IRecorder::start(); rt_recorder_start(rec); }
     void stop() override { IRecorder::stop(); rt_recorder_stop(rec); }
     void write(void* frame, int stride) override { rt_recorder_write(rec, frame, stride); }
+    // (adapter extension, after create) rt_recorder_set_async: depth 1..8 = present() submits the frame to a ring and
+    // writes the older frames that are ready instead of waiting for the frame; 0 = synchronous.  Same files.
+    bool setAsync(int depth) { return rt_recorder_set_async(rec, depth) == RT_OK; }
     rt_recorder handle() const { return rec; }
 
 private:
