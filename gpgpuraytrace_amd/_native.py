@@ -36,6 +36,16 @@ class RtStats(C.Structure):
                 ("ao_steps", C.c_ulonglong), ("noise_wave_iters", C.c_ulonglong)]
 
 
+RT_RAYS_EYE = 1  # rt_ray_options.flags (ABI 9, additive): .eye is the LOD eye (else the compute's Eye)
+RT_RAYS_FORCE_SEGMENTS = 2
+RT_RAYS_FORCE_LANES = 4
+RT_MAX_RAYS = 1 << 26
+
+
+class RtRayOptions(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("eye", C.c_float * 3), ("max_blocks", C.c_uint32)]
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -111,6 +121,8 @@ SIGNATURES = {
     "rt_shard_unpack": (_i, [_vp, _i, _i, _vp]),
     "rt_shard_pack_batch": (_i, [C.POINTER(_vp), C.POINTER(_i), _i, C.POINTER(_vp), _i]),
     "rt_shard_unpack_batch": (_i, [C.POINTER(_vp), C.POINTER(_i), _i, C.POINTER(_vp), _i]),
+    "rt_terrain_trace_rays": (_i, [_vp, _vp, _vp, _i, C.POINTER(RtRayOptions), _vp, _vp]),
+    "rt_terrain_trace_rays_device": (_i, [_vp, _vp, _i, C.POINTER(RtRayOptions), _vp, _vp]),
     "rt_noise_generate": (_i, [C.c_uint32, _i, _vp, _vp]),
     "rt_terrain_set_target_depths": (_i, [_vp, _vp]),
     "rt_recorder_create": (_i, [_vp, _i, _i, _cp, C.POINTER(_vp)]),

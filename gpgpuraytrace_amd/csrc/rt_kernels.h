@@ -126,6 +126,24 @@ void rt_launch_camerarays_batch(const RtLaunch& a);
 void rt_launch_tracescreen(const RtLaunch& a, uint32_t off_x, uint32_t off_y, uint32_t ext_x, uint32_t ext_y,
                            uint32_t tile_first, uint32_t tile_stride);
 
+// A ray query (rt_terrain_trace_rays; camerarays.hlsl:12-21 for rays from memory): n rays packed as
+// ox oy oz _ dx dy dz _ (two float4 each) -> results[n] (float4) and, if set, steps[n] (the march loops'
+// iteration counts), with the launch's landscape, noise tables and constants and `eye` in place of Eye.
+// lpr > 1: one lpr-lane segment per ray in blocks of bs threads (nomadplains; the prepass's pairs: rt_rayquery.h
+// Plan).  lpr == 1: the persistent lane kernel, `blocks` blocks of 1024 threads claiming rays from *counter,
+// which the caller zeroes on the stream before every launch.  false: no such kernel (nothing launched).
+struct RtRayQuery {
+    const float4* rays;
+    float4* results;
+    uint32_t* steps; // may be null
+    uint32_t n;
+    float eye[3];
+    int bs, lpr;
+    uint32_t blocks;
+    uint32_t* counter;
+};
+bool rt_launch_rayquery(const RtLaunch& a, const RtRayQuery& q);
+
 #define RT_TILE 32
 #define RT_FIN_SLOTS 1536 // k_trace's fin pool slots per block
 #define RT_AO_POOL_SLOTS 256 // k_trace's AO counter slots per block (LDS) and their colours (cpool)

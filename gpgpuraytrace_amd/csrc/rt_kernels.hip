@@ -2490,6 +2490,179 @@ void rt_launch_shard_copy(hipStream_t s, const ShardJobs& jobs, int n, int w, in
 }
 
 // ---------------------------------------------------------------------------
+// Ray queries (rt_terrain_trace_rays): camerarays.hlsl:12-21 for rays read from memory instead of
+// getPixelRay's.  Ray i is two 16-byte loads (ox oy oz _ | dx dy dz _), its result one 16-byte store
+// (+ the loop's iteration count with STEPS).  The LOD eye (nomadplains' octave count reads it) is a
+// kernel argument: wave-uniform, and the compute's constant block stays as the frame loop left it.
+namespace {
+
+#ifdef RT_RAYQ_UTIL
+// diagnostic build (scripts/ray_query_bench.py): wave steps and live lanes over them of k_rayquery's waves
+__device__ unsigned long long g_rayq_util[2];
+#endif
+
+struct QueryRay {
+    f3 p, dir;
+};
+__device__ __forceinline__ QueryRay load_query_ray(const float4* __restrict__ rays, uint32_t i)
+{
+    const float4 o = rays[2 * (size_t)i], d = rays[2 * (size_t)i + 1];
+    return QueryRay{rtm::mk(o.x, o.y, o.z), rtm::mk(d.x, d.y, d.z)};
+}
+template <bool STEPS, class M>
+__device__ __forceinline__ void store_query_result(const M& st, float4* __restrict__ out,
+                                                   uint32_t* __restrict__ steps, uint32_t i)
+{
+    RayResult rr = march_result(st);
+    if (rr.density < 0.0f) rr.pd.w = RT_CAMERA_FAR;
+    gstore(out + i, make_float4(rr.pd.x, rr.pd.y, rr.pd.z, rr.pd.w));
+    if constexpr (STEPS) steps[i] = (uint32_t)st.iters;
+}
+
+// Segments (nomadplains, few rays): k_camerarays_group with the ray loaded.  One LPR-lane segment per
+// ray, a static deal: the latency shape of the prepass.
+template <bool STEPS, int BS, int LPR>
+__global__ void __launch_bounds__(BS) k_rayquery_seg(const RtConsts* __restrict__ k,
+                                                      const uint32_t* __restrict__ perm2d,
+                                                      const float4* __restrict__ grad,
+                                                      const float4* __restrict__ rays, float4* __restrict__ out,
+                                                      uint32_t* __restrict__ steps, uint32_t n, float ex, float ey,
+                                                      float ez)
+{
+    constexpr int L = RT_NOMADPLAINS;
+    __shared__ __attribute__((aligned(16))) uint32_t lds[kNoiseLdsWords];
+    load_noise_lds(lds, perm2d, grad, k);
+    const uint32_t i = blockIdx.x * (uint32_t)(BS / LPR) + threadIdx.x / (uint32_t)LPR;
+    if (i >= n) return; // whole segments leave together
+    Ctx c = make_ctx(k, lds);
+    c.eye = rtm::mk(ex, ey, ez);
+    const uint32_t j = threadIdx.x & (LPR - 1u), base = threadIdx.x & 63u & ~(LPR - 1u);
+    const SegOctaves<LPR> g = seg_octaves<LPR>(c, j);
+    const QueryRay r = load_query_ray(rays, i);
+    March<L, false> st;
+    march_begin(c, st, r.p, RT_CAMERA_NEAR, 2.0f, r.dir);
+    while (march_live<L, false, true>(c, st, RT_CAMERA_FAR, 0)) {
+        auto dens = [&](f3 q) {
+            uint32_t used;
+            return density_nomadplains_seg<LPR>(c, g, q, j, base, &used);
+        };
+        march_step_with<L, false, true, decltype(dens), true>(c, st, dens);
+    }
+    if (j == 0) store_query_result<STEPS>(st, out, steps, i);
+}
+
+// Lanes (every landscape, many rays): persistent, one 1024-thread block per CU with the noise tables in
+// LDS once, one lane per ray.  Rays differ in length by more than 100x, so no static deal: a wave whose
+// live lanes fall to `refill_live` or fewer stores its ended rays, claims as many new ones from the
+// query's counter (one atomic per refill, wave_fetch) and hands them to its idle lanes by rank.  Results
+// go to out[ray], so the order of the claims does not show.
+template <int L, bool STEPS>
+__global__ void __launch_bounds__(1024) k_rayquery(const RtConsts* __restrict__ k, const uint32_t* __restrict__ perm2d,
+                                                   const float4* __restrict__ grad, const float4* __restrict__ rays,
+                                                   float4* __restrict__ out, uint32_t* __restrict__ steps, uint32_t n,
+                                                   float ex, float ey, float ez, uint32_t* __restrict__ counter,
+                                                   uint32_t refill_live)
+{
+#ifdef RT_RAYQ_UTIL
+    uint32_t util_wave = 0, util_lane = 0; // this wave's march steps, and its live lanes summed over them
+#endif
+    __shared__ __attribute__((aligned(16))) uint32_t lds[kNoiseLdsWords];
+    load_noise_lds(lds, perm2d, grad, k);
+    Ctx c = make_ctx(k, lds);
+    c.eye = rtm::mk(ex, ey, ez);
+    const uint32_t lane = threadIdx.x & 63u;
+    March<L, false> st{};
+    uint32_t idx = 0;
+    bool has = false, live = false; // has: idx is a ray of the query whose result is not stored yet
+    bool more = true;               // (uniform) the counter has not passed n
+    for (;;) {
+        uint64_t lv = __ballot(live);
+        if (more && (uint32_t)__popcll(lv) <= refill_live) {
+            const uint32_t cnt = 64u - (uint32_t)__popcll(lv); // >= 1: refill_live <= 63
+            const uint32_t first = wave_fetch(counter, lane, cnt);
+            if (!live) {
+                if (has) store_query_result<STEPS>(st, out, steps, idx);
+                idx = first + lane_rank(~lv);
+                has = idx < n;
+                if (has) {
+                    const QueryRay r = load_query_ray(rays, idx);
+                    march_begin(c, st, r.p, RT_CAMERA_NEAR, 2.0f, r.dir);
+                    live = march_live<L, false, true>(c, st, RT_CAMERA_FAR, 0);
+                }
+            }
+            more = first + cnt < n;
+            lv = __ballot(live);
+        }
+        if (!lv) {
+            if (!more) break;
+            continue; // every new ray ended before its first step: claim again
+        }
+#ifdef RT_RAYQ_UTIL
+        ++util_wave;
+        util_lane += (uint32_t)__popcll(lv);
+#endif
+        if (live) {
+            march_step<L, false, true>(c, st);
+            live = march_live<L, false, true>(c, st, RT_CAMERA_FAR, 0);
+        }
+    }
+    if (has) store_query_result<STEPS>(st, out, steps, idx);
+#ifdef RT_RAYQ_UTIL
+    if (lane == 0) {
+        atomicAdd(&g_rayq_util[0], (unsigned long long)util_wave);
+        atomicAdd(&g_rayq_util[1], (unsigned long long)util_lane);
+    }
+#endif
+}
+
+template <int L>
+void launch_rayquery_lanes(const RtLaunch& a, const RtRayQuery& q)
+{
+    // the live-lane count at or below which a wave refills (RT_RAYQ_REFILL; at most 63, so a refill claims >= 1 ray)
+    constexpr uint32_t thr = RT_RAYQ_REFILL < 63 ? RT_RAYQ_REFILL : 63;
+    if (q.steps)
+        hipLaunchKernelGGL((k_rayquery<L, true>), dim3(q.blocks), dim3(1024), 0, a.stream, a.consts, a.perm2d, a.grad,
+                           q.rays, q.results, q.steps, q.n, q.eye[0], q.eye[1], q.eye[2], q.counter, thr);
+    else
+        hipLaunchKernelGGL((k_rayquery<L, false>), dim3(q.blocks), dim3(1024), 0, a.stream, a.consts, a.perm2d, a.grad,
+                           q.rays, q.results, q.steps, q.n, q.eye[0], q.eye[1], q.eye[2], q.counter, thr);
+}
+
+template <int BS, int LPR>
+void launch_rayquery_seg(const RtLaunch& a, const RtRayQuery& q)
+{
+    if (q.steps)
+        hipLaunchKernelGGL((k_rayquery_seg<true, BS, LPR>), dim3(q.blocks), dim3(BS), 0, a.stream, a.consts, a.perm2d,
+                           a.grad, q.rays, q.results, q.steps, q.n, q.eye[0], q.eye[1], q.eye[2]);
+    else
+        hipLaunchKernelGGL((k_rayquery_seg<false, BS, LPR>), dim3(q.blocks), dim3(BS), 0, a.stream, a.consts, a.perm2d,
+                           a.grad, q.rays, q.results, q.steps, q.n, q.eye[0], q.eye[1], q.eye[2]);
+}
+
+} // namespace
+
+bool rt_launch_rayquery(const RtLaunch& a, const RtRayQuery& q)
+{
+    if (q.n == 0 || q.blocks == 0) return true;
+    if (q.lpr > 1) { // segments: the (block size, lanes per ray) pairs of the prepass's ladder
+        if (a.landscape != RT_NOMADPLAINS) return false;
+        if (q.bs == RT_PREPASS_BS1 && q.lpr == RT_PREPASS_LPR1) launch_rayquery_seg<RT_PREPASS_BS1, RT_PREPASS_LPR1>(a, q);
+        else if (q.bs == 512 && q.lpr == 32) launch_rayquery_seg<512, 32>(a, q);
+        else if (q.bs == 512 && q.lpr == 8) launch_rayquery_seg<512, 8>(a, q);
+        else if (q.bs == 512 && q.lpr == 4) launch_rayquery_seg<512, 4>(a, q);
+        else return false;
+        return true;
+    }
+    switch (a.landscape) {
+    case RT_TESTING: launch_rayquery_lanes<RT_TESTING>(a, q); break;
+    case RT_SIMPLE: launch_rayquery_lanes<RT_SIMPLE>(a, q); break;
+    case RT_GREENROCKS: launch_rayquery_lanes<RT_GREENROCKS>(a, q); break;
+    default: launch_rayquery_lanes<RT_NOMADPLAINS>(a, q); break;
+    }
+    return true;
+}
+
+// ---------------------------------------------------------------------------
 // Diagnostics: device evaluation of the numeric primitives, noise3d and
 // getDensity for the primitive-level parity tests (tests/test_gpu_parity.py).
 namespace {
@@ -2630,6 +2803,20 @@ extern "C" int rt_debug_live_hist(unsigned long long* out, int reset)
         if (hipMemcpyToSymbol(HIP_SYMBOL(g_live_hist), zero, 65 * 8) != hipSuccess) return -1;
     }
     return 65;
+}
+#endif
+
+#ifdef RT_RAYQ_UTIL
+// diagnostic build: copies (and with reset != 0 clears) k_rayquery's (wave steps, live lanes summed over them)
+extern "C" int rt_debug_rayquery_util(unsigned long long* out, int reset)
+{
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_rayq_util), 16) != hipSuccess) return -1;
+    if (reset) {
+        static const unsigned long long zero[2] = {};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(g_rayq_util), zero, 16) != hipSuccess) return -1;
+    }
+    return 2;
 }
 #endif
 

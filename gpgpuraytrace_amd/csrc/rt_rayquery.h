@@ -1,0 +1,136 @@
+// rt_rayquery.h -- host-only decisions of rt_terrain_trace_rays (include/frosttrace.h): the option
+// block's validation and the choice of the kernel shape, its lanes per ray and its grid.  No HIP in
+// here: tests/tools/rayquery_check.cpp drives it stand-alone under ASan + UBSan.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
+
+namespace rtq {
+
+constexpr int kMaxRays = 1 << 26;
+// rt_ray_options.flags (RT_RAYS_*)
+constexpr uint32_t kEye = 1u, kForceSegments = 2u, kForceLanes = 4u;
+// the first version of rt_ray_options: size, flags, eye[3], max_blocks
+constexpr uint32_t kOptSizeV1 = 24u;
+// error codes of the C-ABI (RT_OK, RT_ERR_INVALID, RT_ERR_UNSUPPORTED)
+enum { OK = 0, INVALID = -1, UNSUPPORTED = -4 };
+enum Shape { SEGMENTS = 0, LANES = 1 };
+
+// Auto mode on nomadplains: segments up to this many rays, lanes beyond.  A segment march is the prepass's latency
+// shape (one LPR-lane group per ray, a static deal of 128 rays a block at most): about 0.4 ms per round of blocks
+// over the CUs, so it grows with n from 65,536 rays on, while the persistent lane kernel takes about 2.2 ms (its
+// longest ray on one lane) from 1,024 rays to 262,144.  Measured (profiles/r08/ray_query.md): segments 0.97 ms
+// against lanes 2.16 ms at 65,536 rays, 1.77 against 2.21 at 131,072, 2.44 against 2.42 at 196,608, 3.22 against
+// 2.52 at 262,144: the crossing lies between 131,072 and 196,608.
+constexpr int kAutoSegmentsMax = 128 * 1024;
+
+struct Options {
+    uint32_t flags = 0;
+    float eye[3] = {0.0f, 0.0f, 0.0f};
+    uint32_t max_blocks = 0;
+};
+
+// `opt` is the caller's rt_ray_options (may be null: the defaults), read through its size field only as far
+// as the first version reaches; a larger size is a later version whose extra fields this build ignores.
+inline int parse_options(const void* opt, Options* out, const char** why)
+{
+    *out = Options{};
+    if (!opt) return OK;
+    uint32_t size;
+    std::memcpy(&size, opt, 4);
+    if (size < kOptSizeV1) {
+        *why = "rt_ray_options.size is smaller than the struct's first version";
+        return INVALID;
+    }
+    const char* p = static_cast<const char*>(opt);
+    std::memcpy(&out->flags, p + 4, 4);
+    std::memcpy(out->eye, p + 8, 12);
+    std::memcpy(&out->max_blocks, p + 20, 4);
+    if ((out->flags & kForceSegments) && (out->flags & kForceLanes)) {
+        *why = "RT_RAYS_FORCE_SEGMENTS and RT_RAYS_FORCE_LANES are both set";
+        return INVALID;
+    }
+    return OK;
+}
+
+inline int check_count(int n, const char** why)
+{
+    if (n < 0 || n > kMaxRays) {
+        *why = "the ray count must be 0..2^26";
+        return INVALID;
+    }
+    return OK;
+}
+
+struct Plan {
+    int shape = LANES;
+    int bs = 1024, lpr = 1; // threads per block, lanes per ray
+    uint32_t blocks = 0;
+};
+
+// n >= 1 rays; nomadplains: the compute's landscape is it (the only one with a segment shape); cus: the CUs a
+// persistent grid may take; prepass_bs1 / prepass_lpr1: the one-frame prepass's block size and lanes per ray.
+inline int plan(int n, bool nomadplains, uint32_t flags, uint32_t max_blocks, int cus, int prepass_bs1,
+                int prepass_lpr1, Plan* out, const char** why)
+{
+    Plan p;
+    if (flags & kForceSegments) {
+        if (!nomadplains) {
+            *why = "the segment shape exists for nomadplains only";
+            return UNSUPPORTED;
+        }
+        p.shape = SEGMENTS;
+    } else if (flags & kForceLanes) {
+        p.shape = LANES;
+    } else {
+        p.shape = nomadplains && n <= kAutoSegmentsMax ? SEGMENTS : LANES;
+    }
+    if (p.shape == SEGMENTS) {
+        // the prepass's ladder by batch size (launch_camerarays_l), in rays: up to 2 frames the one-frame
+        // shape, up to 4 frames 16 rays of 32 lanes per block, up to 16 frames 64 rays of 8, beyond 128 of 4
+        if (n <= 2 * 1024) {
+            p.bs = prepass_bs1;
+            p.lpr = prepass_lpr1;
+        } else if (n <= 4 * 1024) {
+            p.bs = 512;
+            p.lpr = 32;
+        } else if (n <= 16 * 1024) {
+            p.bs = 512;
+            p.lpr = 8;
+        } else {
+            p.bs = 512;
+            p.lpr = 4;
+        }
+        const uint32_t per_block = (uint32_t)(p.bs / p.lpr);
+        p.blocks = ((uint32_t)n + per_block - 1u) / per_block;
+    } else {
+        p.bs = 1024;
+        p.lpr = 1;
+        uint32_t b = (uint32_t)(cus > 0 ? cus : 1);
+        if (max_blocks && max_blocks < b) b = max_blocks;
+        const uint32_t need = ((uint32_t)n + 1023u) / 1024u;
+        p.blocks = need < b ? need : b;
+    }
+    *out = p;
+    return OK;
+}
+
+// ray i of a packed query: ox oy oz _ dx dy dz _
+inline void pack(const float* origins, const float* dirs, int n, float* packed)
+{
+    for (int i = 0; i < n; ++i) {
+        float* r = packed + (size_t)i * 8;
+        r[0] = origins[3 * (size_t)i];
+        r[1] = origins[3 * (size_t)i + 1];
+        r[2] = origins[3 * (size_t)i + 2];
+        r[3] = 0.0f;
+        r[4] = dirs[3 * (size_t)i];
+        r[5] = dirs[3 * (size_t)i + 1];
+        r[6] = dirs[3 * (size_t)i + 2];
+        r[7] = 0.0f;
+    }
+}
+
+} // namespace rtq

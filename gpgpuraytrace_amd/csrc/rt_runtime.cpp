@@ -32,7 +32,9 @@
 #include "rt_kernels.h"
 #include "rt_math.h"
 #include "rt_noise.h"
+#include "rt_rayquery.h"
 #include "rt_ring.h"
+#include "rt_variants.h"
 
 // RT_DEVICE_DEFERRED with one frame to a launch: frames of fewer pixels render as without the flag (at 256x256 the
 // fused prepass outlasts the frame's trace: 0.642 against 0.585 ms a frame; neutral at 1280x720)
@@ -135,6 +137,7 @@ struct rt_device_s {
     uint32_t* gate = nullptr;  // the gated launch (GatedPrepass): per frame task flags + ray counter
     uint32_t* claims = nullptr; //   and the units claimed per tile of the batch's order
     uint32_t* aocc = nullptr;
+    uint32_t* rq_counter = nullptr; // the ray queries' claim counter (k_rayquery), zeroed on the stream per call
     size_t samples_cap = 0;
     // dominant-kernel timing (rt_device_set_profiling)
     bool profiling = false;
@@ -410,12 +413,25 @@ struct Shader {
     RtConsts* d_consts = nullptr;
     float4* d_grad = nullptr;
     Staging consts_staging, grad_staging;
+    // the ray queries' own device copies of the constant block and permGradients (rt_terrain_trace_rays): a query
+    // between two renders uploads what it needs here, so d_consts, cb_dirty and grad_dirty stay as the frame loop
+    // left them (an ahead or fused prepass is current exactly when it would be without the query)
+    struct QueryConsts {
+        RtConsts* d_consts = nullptr;
+        float4* d_grad = nullptr;
+        RtConsts last{};
+        std::vector<uint8_t> grad_last;
+        bool valid = false;
+        Staging consts_staging, grad_staging;
+    } query;
 
     ~Shader()
     {
         varmgr_forget(this);
         if (d_consts) (void)hipFree(d_consts);
         if (d_grad) (void)hipFree(d_grad);
+        if (query.d_consts) (void)hipFree(query.d_consts);
+        if (query.d_grad) (void)hipFree(query.d_grad);
         for (auto& a : arrays)
             if (a->dev_ptr) (void)hipFree(a->dev_ptr);
     }
@@ -876,7 +892,8 @@ rt_device_s::~rt_device_s()
     }
     for (void* p : {(void*)fb8, (void*)fb32, (void*)stats, (void*)scratch_cam, (void*)queue, (void*)samples,
                     (void*)hitq, (void*)finpool, (void*)cpool, (void*)gate, (void*)claims, (void*)order, (void*)hitmask, (void*)spill_long, (void*)fin, (void*)aocc,
-                    (void*)bgrx, (void*)table.d, (void*)pre_table.d, (void*)fuse_table.d, (void*)fctl, (void*)blocks})
+                    (void*)bgrx, (void*)table.d, (void*)pre_table.d, (void*)fuse_table.d, (void*)fctl, (void*)blocks,
+                    (void*)rq_counter})
         if (p) (void)hipFree(p);
     if (recorder) recorder_detach(recorder); // the recorder outlives its device: it stops capturing
     for (rt_readback_s* rb : rings) ring_detach(rb); // so do its rings: later calls return RT_ERR_STATE
@@ -2598,6 +2615,130 @@ extern "C" int rt_debug_sky(rt_compute c, const float* dirs, float* out, int n)
     HIP_TRY(hipFree(dx));
     HIP_TRY(hipFree(dy));
     return RT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// rt_terrain_trace_rays: caller-supplied rays marched as the prepass marches its own (include/frosttrace.h)
+namespace {
+
+// the compute's constants and gradients as they are NOW, in the query's own device copies (Shader::query)
+int sync_query_consts(rt_device dev, Shader* s, float default_eye[3])
+{
+    Shader::QueryConsts& q = s->query;
+    if (!q.d_consts) HIP_TRY(hipMalloc(&q.d_consts, sizeof(RtConsts)));
+    if (!q.d_grad) HIP_TRY(hipMalloc(&q.d_grad, 128 * sizeof(float4)));
+    RtConsts hk;
+    std::vector<uint8_t> grad(128 * sizeof(float4), 0);
+    {
+        std::lock_guard<std::mutex> lk(g_cb_mu);
+        build_consts(*s, *dev, hk);
+        const auto& nz = s->cb[CB_NOISE];
+        memcpy(grad.data(), nz.data(), std::min(grad.size(), nz.size()));
+    }
+    for (int i = 0; i < 3; ++i) default_eye[i] = hk.eye[i];
+    if (q.valid && !memcmp(&hk, &q.last, sizeof(RtConsts)) && grad == q.grad_last) return RT_OK;
+    q.valid = false;
+    if (int rc = q.consts_staging.upload(dev->stream, q.d_consts, &hk, sizeof(RtConsts))) return rc;
+    if (int rc = q.grad_staging.upload(dev->stream, q.d_grad, grad.data(), grad.size())) return rc;
+    q.last = hk;
+    q.grad_last = grad;
+    q.valid = true;
+    return RT_OK;
+}
+
+// plan and enqueue one query of n >= 1 rays on the device stream (no host synchronisation)
+int trace_rays_enqueue(rt_compute c, const void* rays_device, int n, const rtq::Options& o, void* results_device,
+                       void* steps_device)
+{
+    rt_device dev = c->dev;
+    Shader* s = c->shader;
+    float eye[3];
+    if (int rc = sync_query_consts(dev, s, eye)) return rc;
+    if (o.flags & rtq::kEye) memcpy(eye, o.eye, sizeof(eye));
+    rtq::Plan p;
+    const char* why = "";
+    if (int rc = rtq::plan(n, s->landscape == RT_NOMADPLAINS, o.flags, o.max_blocks, dev->num_cus - dev->reserve_cus,
+                           RT_PREPASS_BS1, RT_PREPASS_LPR1, &p, &why))
+        return fail(rc, "rt_terrain_trace_rays: %s", why);
+    RtLaunch a = make_launch(dev, s);
+    a.consts = s->query.d_consts;
+    a.grad = s->query.d_grad;
+    RtRayQuery q{};
+    q.rays = (const float4*)rays_device;
+    q.results = (float4*)results_device;
+    q.steps = (uint32_t*)steps_device;
+    q.n = (uint32_t)n;
+    memcpy(q.eye, eye, sizeof(eye));
+    q.bs = p.bs;
+    q.lpr = p.lpr;
+    q.blocks = p.blocks;
+    if (p.shape == rtq::LANES) {
+        if (!dev->rq_counter) HIP_TRY(hipMalloc(&dev->rq_counter, 64));
+        HIP_TRY(hipMemsetAsync(dev->rq_counter, 0, 4, dev->stream));
+        q.counter = dev->rq_counter;
+    }
+    if (!rt_launch_rayquery(a, q)) return fail(RT_ERR_UNSUPPORTED, "rt_terrain_trace_rays: no kernel for this shape");
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+// the checks both forms share, in the order the header gives; *o: the parsed options
+int trace_rays_check(rt_compute c, int n, const rt_ray_options* opt, rtq::Options* o)
+{
+    if (!c) return fail(RT_ERR_INVALID, "null compute");
+    const char* why = "";
+    if (int rc = rtq::check_count(n, &why)) return fail(rc, "rt_terrain_trace_rays: %s", why);
+    if (int rc = rtq::parse_options(opt, o, &why)) return fail(rc, "rt_terrain_trace_rays: %s", why);
+    if (!c->shader) return fail(RT_ERR_STATE, "no current shader");
+    if ((o->flags & rtq::kForceSegments) && c->shader->landscape != RT_NOMADPLAINS)
+        return fail(RT_ERR_UNSUPPORTED, "rt_terrain_trace_rays: the segment shape exists for nomadplains only");
+    return RT_OK;
+}
+
+} // namespace
+
+extern "C" int rt_terrain_trace_rays_device(rt_compute c, const void* rays_device, int n, const rt_ray_options* opt,
+                                            void* results_device, void* steps_device)
+{
+    rtq::Options o;
+    if (int rc = trace_rays_check(c, n, opt, &o)) return rc;
+    if (n > 0 && (!rays_device || !results_device)) return fail(RT_ERR_INVALID, "rt_terrain_trace_rays_device: null rays or results");
+    if (int rc = check_texture(c->shader)) return rc;
+    if (int rc = host_flag_check(c->dev)) return rc;
+    if (n == 0) return RT_OK;
+    HIP_TRY(hipSetDevice(c->dev->ordinal));
+    return trace_rays_enqueue(c, rays_device, n, o, results_device, steps_device);
+}
+
+extern "C" int rt_terrain_trace_rays(rt_compute c, const float* origins, const float* dirs, int n,
+                                     const rt_ray_options* opt, float* results, uint32_t* steps)
+{
+    rtq::Options o;
+    if (int rc = trace_rays_check(c, n, opt, &o)) return rc;
+    if (n > 0 && (!origins || !dirs || !results)) return fail(RT_ERR_INVALID, "rt_terrain_trace_rays: null origins, dirs or results");
+    if (int rc = check_texture(c->shader)) return rc;
+    if (int rc = host_flag_check(c->dev)) return rc;
+    if (n == 0) return RT_OK;
+    rt_device dev = c->dev;
+    HIP_TRY(hipSetDevice(dev->ordinal));
+    // one device block: the packed rays, the results, the step counts
+    const size_t nr = (size_t)n, rays_b = nr * 32, res_b = nr * 16, steps_b = steps ? nr * 4 : 0;
+    std::vector<float> packed(nr * 8);
+    rtq::pack(origins, dirs, n, packed.data());
+    char* d = nullptr;
+    HIP_TRY(hipMalloc(&d, rays_b + res_b + steps_b));
+    auto run = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(d, packed.data(), rays_b, hipMemcpyHostToDevice, dev->stream));
+        if (int rc = trace_rays_enqueue(c, d, n, o, d + rays_b, steps ? d + rays_b + res_b : nullptr)) return rc;
+        HIP_TRY(hipMemcpyAsync(results, d + rays_b, res_b, hipMemcpyDeviceToHost, dev->stream));
+        if (steps) HIP_TRY(hipMemcpyAsync(steps, d + rays_b + res_b, steps_b, hipMemcpyDeviceToHost, dev->stream));
+        HIP_TRY(hipStreamSynchronize(dev->stream));
+        return RT_OK;
+    };
+    const int rc = run();
+    if (rc) (void)hipStreamSynchronize(dev->stream); // whatever was queued is over before the block is freed
+    (void)hipFree(d);
+    return rc;
 }
 
 // ---------------------------------------------------------------------------

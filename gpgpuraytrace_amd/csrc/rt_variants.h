@@ -144,6 +144,18 @@
 #define RT_PREPASS_LPR1 16
 #endif
 
+// k_rayquery (the ray queries' lane shape): a wave refills its idle lanes from the query's counter once its live
+// lanes are this many or fewer (0: only when all have ended; 63: as soon as one ends).  A refill is one atomic
+// round trip the wave waits for.  2^20 nomadplains rays, ms per query (lane utilisation over the march steps), in
+// grid order / shuffled: 0: 5.37 (95%) / 9.18 (47%), 32: 6.33 / 8.66, 48: 5.84 (92%) / 8.26 (71%), 56: 5.77 (94%)
+// / 8.01 (74%), 63: 6.43 (93%) / 10.68 (76%) -- rays alike in length (grid order) lose little by waiting for the
+// whole wave, unlike ones lose half their lanes; one atomic per ended ray (63) costs more than the lanes it fills.
+// 56, the long-ray loop's compaction rule, is the best shuffled and within 8% of the best in grid order
+// (profiles/r08/ray_query.md)
+#ifndef RT_RAYQ_REFILL
+#define RT_RAYQ_REFILL 56
+#endif
+
 // (A/B) noise3d's z-layer replication t + Z * 0x01010101 as an inline v_mad_u32_u24
 #ifndef RT_Z_MAD24
 #define RT_Z_MAD24 0

@@ -633,6 +633,68 @@ class Terrain:
         self.camera_view[:] = out
         return self.camera_view
 
+    def trace_rays(self, origins, dirs, eye=None, steps=False, mode="auto", max_blocks=0):
+        """rt_terrain_trace_rays: what n rays of the caller's own hit, marched as the prepass marches its
+        pixel rays (camerarays.hlsl:12-21).  origins, dirs: (n, 3); dirs are used as given (their length enters
+        the first step).  eye: the level-of-detail eye (default: the camera's, the compute's current Eye).
+        Returns results (n, 4) float32 -- the last sample's position and the hit distance, 5000 for a miss --
+        or (results, steps) with the march loops' iteration counts (n,) uint32; None if the call fails
+        (lib().rt_last_error()).  mode: "auto", "segments" (nomadplains only) or "lanes"; max_blocks caps the
+        lanes shape's persistent grid.  Blocking; uses the camerarays compute; needs set_camera() first."""
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise ValueError("trace_rays: %d origins, %d dirs" % (len(o), len(d)))
+        n = len(o)
+        opt = ray_options(eye, mode, max_blocks)
+        self.update_shaders()
+        res = np.empty((n, 4), np.float32)
+        st = np.empty(n, np.uint32) if steps else None
+        rc = lib().rt_terrain_trace_rays(self.camera_compute._h, o.ctypes.data, d.ctypes.data, n, C.byref(opt),
+                                         res.ctypes.data, st.ctypes.data if steps else None)
+        if rc != _native.RT_OK:
+            return None
+        return (res, st) if steps else res
+
+    def trace_rays_device(self, rays_ptr, n, results_ptr, steps_ptr=0, eye=None, mode="auto", max_blocks=0):
+        """rt_terrain_trace_rays_device: the same for device arrays -- rays_ptr n x 8 float32 (pack_rays'
+        layout), results_ptr n x 4 float32, steps_ptr n uint32 or 0 -- enqueued on the device's stream with no
+        host synchronisation (order other streams with Device.wait_event / record_event).  True on success."""
+        opt = ray_options(eye, mode, max_blocks)
+        self.update_shaders()
+        rc = lib().rt_terrain_trace_rays_device(self.camera_compute._h, rays_ptr or None, int(n), C.byref(opt),
+                                                results_ptr or None, steps_ptr or None)
+        return rc == _native.RT_OK
+
+
+RAY_MODES = {"auto": 0, "segments": _native.RT_RAYS_FORCE_SEGMENTS, "lanes": _native.RT_RAYS_FORCE_LANES}
+
+
+def ray_options(eye=None, mode="auto", max_blocks=0):
+    """An rt_ray_options block: the LOD eye (None: the compute's Eye), the kernel shape, the lanes grid's cap."""
+    if mode not in RAY_MODES:
+        raise ValueError("ray query mode %r: one of %s" % (mode, sorted(RAY_MODES)))
+    opt = _native.RtRayOptions()
+    opt.size = C.sizeof(_native.RtRayOptions)
+    opt.flags = RAY_MODES[mode]
+    if eye is not None:
+        opt.flags |= _native.RT_RAYS_EYE
+        opt.eye[:] = [float(x) for x in np.asarray(eye, np.float32).reshape(3)]
+    opt.max_blocks = int(max_blocks)
+    return opt
+
+
+def pack_rays(origins, dirs):
+    """The device form's ray layout: (n, 8) float32 rows ox oy oz 0 dx dy dz 0 (two 16-byte loads per ray)."""
+    o = np.asarray(origins, np.float32).reshape(-1, 3)
+    d = np.asarray(dirs, np.float32).reshape(-1, 3)
+    if o.shape != d.shape:
+        raise ValueError("pack_rays: %d origins, %d dirs" % (len(o), len(d)))
+    out = np.zeros((len(o), 8), np.float32)
+    out[:, 0:3] = o
+    out[:, 4:7] = d
+    return out
+
 
 def render_batch(terrains, shard_rank=0, shard_count=1):
     """rt_terrain_render_batch: Terrain.render_device for up to 24 Terrains at once (RT_MAX_BATCH) (one GPU,

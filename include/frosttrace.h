@@ -402,6 +402,50 @@ int rt_noise_generate(uint32_t seed, int rand_kind, uint8_t* perm2d, float* grad
  * CellDistance float2[1024], for engines that keep the reference's readback round trip. */
 int rt_terrain_set_target_depths(const float* camera_results, float* cell_distance);
 
+/* ---- ray queries (ABI 9, additive; no reference counterpart) ----
+ * What a ray of the host's own hits: picking, placement, collision (Gameplay/Flyby.cpp:44-90 reads the prepass
+ * hits for this, along the 1024 directions of the last frame only), height and depth maps.  A query is n rays
+ * (origin_i, dir_i) and one LOD eye E per call; the compute supplies the landscape, the noise tables and the
+ * landscape constants (either kind of compute, camerarays or tracescreen).  Result i is the CameraResults
+ * element camerarays.hlsl:12-21 would have written for a pixel ray with p = origin_i and dir = dir_i:
+ *     rr = traceRay(origin_i, 0.01, 5000, stepmod 2, dir_i, calcfog off, skiprefine on)    (tracing.hlsl:47-105)
+ *     result_i = float4(rr.pd.xyz, rr.density < 0 ? 5000 : rr.pd.w),  steps_i = the loop's iteration count
+ * so a hit is result.w < 5000, bit for bit what a prepass of such a camera stores.
+ *   dir   is used as given, as the prepass uses its un-normalised p - Eye: its LENGTH enters the first step
+ *         (tracing.hlsl:54), and the march then runs along dir / |dir|.  A zero dir gives (0, 0, 0, 0.01) and
+ *         0 steps.  Non-finite inputs give unspecified results (the march still ends).
+ *   E     replaces Eye wherever the density reads it (nomadplains' octave count, length(p - Eye)): the query
+ *         sees the terrain at the level of detail the viewer at E sees.  Without RT_RAYS_EYE it is the compute's
+ *         current Eye variable.  One per call, not per ray.
+ *   No step cap (the prepass passes none); results in ray order.
+ * rt_ray_options (opt may be NULL: all defaults): size = sizeof(rt_ray_options) of the caller's header (later
+ *   versions append fields); RT_RAYS_FORCE_SEGMENTS / RT_RAYS_FORCE_LANES pick the kernel shape (default: by n
+ *   and landscape; identical bits either way): segments march one ray on a group of lanes (nomadplains only:
+ *   RT_ERR_UNSUPPORTED elsewhere; the prepass's latency shape, for few rays), lanes march a ray per lane in a
+ *   persistent grid whose waves refill from a counter (every landscape; the throughput shape).  max_blocks
+ *   caps that grid (0: every CU less rt_device_reserve_cus).
+ * rt_terrain_trace_rays: host arrays, xyz interleaved (origins, dirs: 3n floats; results: 4n floats; steps: n
+ *   uint32 or NULL); blocking, like rt_array_map.
+ * rt_terrain_trace_rays_device: device arrays (rays: n x 8 floats ox oy oz _ dx dy dz _, 16-byte aligned;
+ *   results n x 4 floats; steps n uint32 or NULL), enqueued on the compute's device stream with no host
+ *   synchronisation: order other streams with rt_device_wait_event / rt_device_record_event.
+ * Both: n == 0 is RT_OK and launches nothing.  RT_ERR_INVALID: n < 0, n > 2^26, a NULL compute or required
+ *   array, opt->size below the first version (24), both force flags.  RT_ERR_STATE without texPerm2D bound, or
+ *   with the fail-safe word set.  A query reads no frame state and changes none: it flushes no deferred frame,
+ *   invalidates no ahead / fused prepass or captured graph, and uploads the constants it needs to a copy of
+ *   its own, so it may run between any two renders. */
+enum { RT_RAYS_EYE = 1, RT_RAYS_FORCE_SEGMENTS = 2, RT_RAYS_FORCE_LANES = 4 };
+typedef struct {
+    uint32_t size;
+    uint32_t flags;
+    float eye[3];
+    uint32_t max_blocks;
+} rt_ray_options;
+int rt_terrain_trace_rays(rt_compute cs, const float* origins, const float* dirs, int n,
+                          const rt_ray_options* opt, float* results, uint32_t* steps);
+int rt_terrain_trace_rays_device(rt_compute cs, const void* rays_device, int n,
+                                 const rt_ray_options* opt, void* results_device, void* steps_device);
+
 /* ---- diagnostics (primitive-level parity tests; no reference counterpart) ----
  * rt_debug_math: device evaluation of the numeric primitives of DESIGN.md §Numerics
  *   (op 0 exp2, 1 log2, 2 exp, 3 sin, 4 cos, 5 sqrt, 6 rcp, 7 rsqrt, 8 pow, 9 max,

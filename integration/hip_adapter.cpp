@@ -77,6 +77,17 @@ void ComputeHIP::setTexture(int stage, ITexture* texture)
     rt_compute_set_texture(cs, stage, t ? t->handle() : nullptr);
 }
 
+bool ComputeHIP::traceRays(const float* origins, const float* dirs, int n, float* results, const float* eye)
+{
+    rt_ray_options opt = {};
+    opt.size = (uint32_t)sizeof(opt);
+    if (eye) {
+        opt.flags = RT_RAYS_EYE;
+        for (int i = 0; i < 3; ++i) opt.eye[i] = eye[i];
+    }
+    return rt_terrain_trace_rays(cs, origins, dirs, n, &opt, results, nullptr) == RT_OK;
+}
+
 DeviceHIP::DeviceHIP(IWindow* window) : IDevice(kDeviceApiHip, window) { }
 DeviceHIP::~DeviceHIP()
 {

@@ -76,6 +76,12 @@ public:
     IShaderBuffer* getBuffer(const std::string& name) override;
     bool swap() override;
     void setTexture(int stage, ITexture* texture) override;
+    // (adapter extension) rt_terrain_trace_rays (ABI 9, additive): what n rays of the host's own hit, marched as
+    // camerarays.hlsl:12-21 marches its pixel rays with this compute's landscape, tables and constants.  origins,
+    // dirs: 3n floats (dirs as given: their length enters the first step); results: 4n floats (the last sample's
+    // position, the hit distance or 5000 for a miss); eye: the level-of-detail eye (3 floats), nullptr = the
+    // compute's Eye variable.  Blocking.  The reference's only hit query is the last prepass (Flyby.cpp:44-90).
+    bool traceRays(const float* origins, const float* dirs, int n, float* results, const float* eye = nullptr);
     rt_compute handle() const { return cs; }
 
 private:
