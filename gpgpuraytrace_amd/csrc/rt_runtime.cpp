@@ -33,12 +33,13 @@
 #include "rt_math.h"
 #include "rt_noise.h"
 #include "rt_rayquery.h"
+#include "rt_render_route.h"
 #include "rt_ring.h"
 #include "rt_variants.h"
 
-// RT_DEVICE_DEFERRED with one frame to a launch: frames of fewer pixels render as without the flag (at 256x256 the
-// fused prepass outlasts the frame's trace: 0.642 against 0.585 ms a frame; neutral at 1280x720)
-#define RT_DEFER_FUSE_MIN_PIXELS ((size_t)1280 * 720)
+static_assert(rtr::kStats == RT_DEVICE_STATS && rtr::kGraph == RT_DEVICE_GRAPH && rtr::kGated == RT_DEVICE_GATED &&
+                  rtr::kDeferred == RT_DEVICE_DEFERRED && rtr::kDebugDeferSmall == RT_DEVICE_DEBUG_DEFER_SMALL,
+              "rt_render_route.h restates the device flags");
 
 namespace {
 
@@ -60,6 +61,13 @@ int fail(int code, const char* fmt, ...)
         hipError_t e_ = (expr);                                                              \
         if (e_ != hipSuccess) return fail(RT_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
+
+// the events that order streams are made on first use
+int ensure_event(hipEvent_t& ev)
+{
+    if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    return RT_OK;
+}
 
 std::mutex g_vfs_mu;
 std::vector<std::string> g_vfs;
@@ -99,7 +107,7 @@ struct Staging {
             bytes = n;
             pending = false;
         }
-        if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        if (int rc = ensure_event(ev)) return rc;
         if (pending) HIP_TRY(hipEventSynchronize(ev));
         memcpy(host, src, n);
         HIP_TRY(hipMemcpyAsync(dst, host, n, hipMemcpyHostToDevice, s));
@@ -672,7 +680,7 @@ int host_flag_check(rt_device d)
 
 RtLaunch make_launch(rt_device dev, Shader* s)
 {
-    RtLaunch a;
+    RtLaunch a{}; // (what a launch leaves alone is off: no fit, no fused, waited-for or gated prepass, not packed)
     a.stream = dev->stream;
     a.landscape = s->landscape;
     a.consts = s->d_consts;
@@ -687,27 +695,16 @@ RtLaunch make_launch(rt_device dev, Shader* s)
     a.hitq = dev->hitq;
     a.spill_long = dev->spill_long;
     rt_spill_caps(s->aa, s->ao, &a.hit_cap, &a.long_spill_cap);
-    a.cells_from_cam = 0;
     a.small_rings = (dev->flags & RT_DEVICE_DEBUG_SMALL_RINGS) ? 1 : 0;
-    a.fit = 0;
     a.fin = dev->fin;
     a.finpool = dev->finpool;
     a.cpool = dev->cpool;
-    a.fitm = 0;
     a.aocc = dev->aocc;
     a.ao_samples = s->ao;
     a.aa = s->aa;
     a.frames = dev->table.d;
-    a.frames_host = FrameTable{};
     a.n_frames = 1;
-    a.after_order = nullptr;
-    a.fuse_next = FusedPrepass{nullptr, nullptr, 0u};
-    a.wait_ctl = nullptr;
-    a.wait_total = 0;
-    a.after_order_fuse = nullptr;
     a.host_flag = host_flag_device(dev->ordinal);
-    a.gated = GatedPrepass{nullptr, nullptr, 0u, 0u};
-    a.packed = 0;
     return a;
 }
 
@@ -1536,10 +1533,16 @@ void* rt_array_device_pointer(rt_array a) // (the caller reads it behind the fra
 }
 
 // ---- Terrain::render on the device -------------------------------------------
-// PH_STAGE (rt_terrain_prepass_ahead, fused): upload the camerarays constants and the frame table a
-// fusing k_trace reads, launch nothing.  PH_KEEP (with PH_TRACE; RT_DEVICE_DEFERRED): upload no constant
-// block -- the frame's went up when it was rendered, and the host copies may hold the next frame's since
-enum { PH_PRE = 1, PH_TRACE = 2, PH_STAGE = 4, PH_KEEP = 8 };
+// The frames of one call: n (camerarays, tracescreen) compute pairs, as the caller passed them (batch_begin
+// validates them, once, into a Batch).
+struct Frames {
+    const rt_compute* cams = nullptr;
+    const rt_compute* scrs = nullptr;
+    int n = 0;
+};
+struct Shard {
+    int rank = 0, count = 1;
+};
 // the tracescreen launch's fused-prepass roles (FusedPrepass): the next batch's prepass it runs, and
 // the wait of its k_order for this batch's prepass that the previous k_trace ran
 struct TraceFuse {
@@ -1548,82 +1551,25 @@ struct TraceFuse {
     const uint32_t* wait_ctl = nullptr;
     uint32_t wait_total = 0;
 };
-static int terrain_render_batch(const rt_compute* cams, const rt_compute* scrs, int n, int shard_rank,
-                                int shard_count, bool feed, int phases = PH_PRE | PH_TRACE, int first = 0,
-                                int count = -1, float4* camera_out = nullptr, const float4* camera_in = nullptr,
-                                const TraceFuse* fuse = nullptr, uint8_t* packed_dst = nullptr,
-                                size_t packed_stride = 0);
-
-// Terrain::render (Terrain.cpp:105-136), one frame per call on the device's stream.  Frame i+1's
-// camerarays prepass needs only frame i's k_order to be done (the last reader of CameraResults): on the
-// device's own prepass stream it waits for that k_order (ev_order, recorded between k_order and k_trace)
-// and so runs in frame i's trace tail, where the persistent k_trace's blocks retire, instead of after
-// the whole frame; the trace waits for it (ev_pre).  Same launches, same bits.  The first frame, and a
-// frame after anything else read this device's CameraResults on its stream (a feed render, an ahead or
-// fused prepass, a batch), prepass in line; so do the instrumented, graph and gated devices.
-static int deferred_render(rt_device d, rt_compute cam, rt_compute scr, int shard_rank, int shard_count);
-static int serial_render(rt_device d, rt_compute cam, rt_compute scr, int shard_rank, int shard_count);
-
-int rt_terrain_render(rt_compute cam, rt_compute scr, int shard_rank, int shard_count)
-{
-    rt_device d = (cam && scr && scr->dev && cam->dev == scr->dev) ? scr->dev : nullptr;
-    if (d && (d->flags & RT_DEVICE_DEFERRED)) return deferred_render(d, cam, scr, shard_rank, shard_count);
-    return serial_render(d, cam, scr, shard_rank, shard_count);
-}
-
-static int serial_render(rt_device d, rt_compute cam, rt_compute scr, int shard_rank, int shard_count)
-{
-    const bool plain = d && !(d->flags & (RT_DEVICE_GRAPH | RT_DEVICE_STATS | RT_DEVICE_GATED)) && d->stream &&
-                       !d->ahead_pending && !d->ahead_in_pending && d->fuse_state == rt_device_s::FUSE_NONE;
-    if (!plain) {
-        if (d) d->serial_ok = false;
-        return terrain_render_batch(&cam, &scr, 1, shard_rank, shard_count, false);
-    }
-    if (int rc0 = host_flag_check(d)) return rc0;
-    HIP_TRY(hipSetDevice(d->ordinal));
-    if (!d->ev_order) HIP_TRY(hipEventCreateWithFlags(&d->ev_order, hipEventDisableTiming));
-    if (!(d->serial_ok && d->order_recorded)) {
-        int rc = terrain_render_batch(&cam, &scr, 1, shard_rank, shard_count, false); // records ev_order
-        d->serial_ok = rc == RT_OK;
-        return rc;
-    }
-    if (!d->pre_stream) HIP_TRY(hipStreamCreateWithFlags(&d->pre_stream, hipStreamNonBlocking));
-    if (!d->ev_pre) HIP_TRY(hipEventCreateWithFlags(&d->ev_pre, hipEventDisableTiming));
-    HIP_TRY(hipStreamWaitEvent(d->pre_stream, d->ev_order, 0));
-    hipStream_t main = d->stream;
-    d->stream = d->pre_stream; // the prepass-only call uploads the camerarays constants and launches there
-    int rc = terrain_render_batch(&cam, &scr, 1, 0, 1, false, PH_PRE);
-    d->stream = main;
-    if (rc) {
-        d->serial_ok = false;
-        return rc;
-    }
-    HIP_TRY(hipEventRecord(d->ev_pre, d->pre_stream));
-    HIP_TRY(hipStreamWaitEvent(main, d->ev_pre, 0));
-    rc = terrain_render_batch(&cam, &scr, 1, shard_rank, shard_count, false, PH_TRACE);
-    d->serial_ok = rc == RT_OK;
-    if (rc == RT_OK) { // a render with a prepass launch (rt_device_info), on the prepass stream
-        ++d->prepass_launches;
-        ++d->prestream_renders;
-    }
-    return rc;
-}
-
-int rt_terrain_render_feed(rt_compute cam, rt_compute scr, int shard_rank, int shard_count)
-{
-    if (cam && cam->dev) cam->dev->serial_ok = false; // its CameraResults copy follows the prepass
-    return terrain_render_batch(&cam, &scr, 1, shard_rank, shard_count, true);
-}
-
-int rt_terrain_feed_wait(rt_compute cam, float* camera_results)
-{
-    if (!cam || !camera_results) return fail(RT_ERR_INVALID, "bad arguments");
-    if (!cam->feed_pending) return fail(RT_ERR_STATE, "no camera feed pending (rt_terrain_render_feed)");
-    HIP_TRY(hipEventSynchronize(cam->feed_ev));
-    memcpy(camera_results, cam->feed_host, 1024 * sizeof(float4));
-    cam->feed_pending = false;
-    return RT_OK;
-}
+// batch_prepass: the frames [first, first + count) (count < 0: all of them), into the frames' CameraResults
+// or, for the split prepass of rt_terrain_prepass_batch, into a contiguous device buffer (n x 1024 float4)
+struct PrepassOpts {
+    int first = 0, count = -1;
+    float4* camera_out = nullptr;
+};
+// batch_trace: setTargetDepths + tracescreen of the frames
+struct TraceOpts {
+    bool prepass = false;     // the frames' prepass runs in line before it (a full render)
+    bool feed = false;        // rt_terrain_render_feed: the CameraResults go to the host behind the prepass
+    // RT_DEVICE_DEFERRED: upload no constant block -- the frame's went up when it was rendered, and the host
+    // copies may hold the next frame's since
+    bool keep_consts = false;
+    const float4* camera_in = nullptr; // rt_terrain_trace_batch: the batch's gathered CameraResults
+    TraceFuse fuse;
+    uint8_t* packed_dst = nullptr; // rt_terrain_render_batch_packed: frame f's shard pixels go to
+    size_t packed_stride = 0;      //   packed_dst + f * packed_stride
+    Shard shard;
+};
 
 extern "C++" {
 namespace {
@@ -1691,9 +1637,10 @@ void key_frames(std::vector<uint64_t>& k, const FrameTable& ft)
     k.insert(k.end(), w, w + sizeof(FrameTable) / sizeof(uint64_t));
 }
 
-// A validated batch: its frame table, the device it runs on (frame 0's: stream, buffers,
-// counters) and whether frames live on other devices.
+// A validated batch: its frames, their frame table, the device it runs on (frame 0's: stream,
+// buffers, counters) and whether frames live on other devices.
 struct Batch {
+    Frames fr;
     FrameTable ft{};
     rt_device dev = nullptr;
     const Shader* s0 = nullptr;
@@ -1702,9 +1649,11 @@ struct Batch {
 
 // Check the n (camerarays, tracescreen) pairs, upload their constants, build the frame table
 // and order the other frames' device streams before the batch.
-int batch_begin(const rt_compute* cams, const rt_compute* scrs, int n, Batch& b, bool sync_cam = true,
-                bool sync_scr = true)
+int batch_begin(const Frames& fr, Batch& b, bool sync_cam, bool sync_scr)
 {
+    const rt_compute *cams = fr.cams, *scrs = fr.scrs;
+    const int n = fr.n;
+    b.fr = fr;
     if (!cams || !scrs || n < 1 || n > RT_MAX_BATCH) return fail(RT_ERR_INVALID, "a batch holds 1..%d frames", RT_MAX_BATCH);
     int rc;
     for (int f = 0; f < n; ++f) {
@@ -1746,7 +1695,7 @@ int batch_begin(const rt_compute* cams, const rt_compute* scrs, int n, Batch& b,
         rt_device d = scrs[f]->dev;
         if (d == b.dev) continue;
         b.others = true;
-        if (!d->sync_ev) HIP_TRY(hipEventCreateWithFlags(&d->sync_ev, hipEventDisableTiming));
+        if (int rc = ensure_event(d->sync_ev)) return rc;
         HIP_TRY(hipEventRecord(d->sync_ev, d->stream));
         HIP_TRY(hipStreamWaitEvent(b.dev->stream, d->sync_ev, 0));
     }
@@ -1754,12 +1703,14 @@ int batch_begin(const rt_compute* cams, const rt_compute* scrs, int n, Batch& b,
 }
 
 // the other frames' devices see their frames complete in their own stream order
-int batch_end(const rt_compute* scrs, int n, Batch& b)
+int batch_end(const Batch& b)
 {
     HIP_TRY(hipGetLastError());
     if (!b.others) return RT_OK;
+    const rt_compute* scrs = b.fr.scrs;
+    const int n = b.fr.n;
     rt_device dev = b.dev;
-    if (!dev->sync_ev) HIP_TRY(hipEventCreateWithFlags(&dev->sync_ev, hipEventDisableTiming));
+    if (int rc = ensure_event(dev->sync_ev)) return rc;
     HIP_TRY(hipEventRecord(dev->sync_ev, dev->stream));
     for (int f = 1; f < n; ++f)
         if (scrs[f]->dev != dev) HIP_TRY(hipStreamWaitEvent(scrs[f]->dev->stream, dev->sync_ev, 0));
@@ -1768,26 +1719,35 @@ int batch_end(const rt_compute* scrs, int n, Batch& b)
 
 } // namespace
 
-// Terrain::render (Terrain.cpp:105-136) for n frames at once: every frame's prepass and
-// setTargetDepths in one launch each, then one tracescreen over all frames' units
-// (frame-major), on frame 0's device stream and buffers.  Frames on other devices (a
-// FrameRing's slots) are ordered around the batch with events.  Phases: PRE = prepass,
-// TRACE = setTargetDepths + tracescreen; `first`/`count` select the prepass frames,
-// camera_out / camera_in redirect CameraResults through a contiguous device buffer
-// (n x 1024 float4) for the split prepass of rt_terrain_prepass_batch / rt_terrain_trace_batch.
-static int terrain_render_batch(const rt_compute* cams, const rt_compute* scrs, int n, int shard_rank,
-                                int shard_count, bool feed, int phases, int first, int count, float4* camera_out,
-                                const float4* camera_in, const TraceFuse* fuse, uint8_t* packed_dst,
-                                size_t packed_stride)
+// The head of every call that launches on the frames' devices: the GPU's fail-safe flag (on the lead), then a
+// deferred frame of each device goes first.  (The frames are not validated yet: batch_begin reports them.)
+static int devices_enter(const Frames& fr)
 {
-    if (shard_count < 1 || shard_rank < 0 || shard_rank >= shard_count) return fail(RT_ERR_INVALID, "bad shard");
-    if (feed && n != 1) return fail(RT_ERR_INVALID, "the camera feed is per frame");
-    if (scrs && n >= 1 && scrs[0] && scrs[0]->dev)
+    const rt_compute* scrs = fr.scrs;
+    if (scrs && fr.n >= 1 && scrs[0] && scrs[0]->dev)
         if (int rc0 = host_flag_check(scrs[0]->dev)) return rc0;
-    for (int f = 0; scrs && f < n && f < RT_MAX_BATCH; ++f) // a deferred frame of these devices goes first
+    for (int f = 0; scrs && f < fr.n && f < RT_MAX_BATCH; ++f)
         if (scrs[f] && scrs[f]->dev)
             if (int rc0 = defer_flush(scrs[f]->dev)) return rc0;
-    if (cams && scrs && n >= 1 && n <= RT_MAX_BATCH && scrs[0] && scrs[0]->dev) {
+    return RT_OK;
+}
+
+// what the operation behind the entry step does with the frames, as far as the entry's rules go (neither
+// prepass nor trace: batch_stage)
+struct Entry {
+    bool prepass = false, trace = false;
+    bool keep_consts = false;
+};
+
+// The entry step of batch_stage, batch_prepass and batch_trace, in this order: flag check and flushes
+// (devices_enter), the waits for a pending ahead prepass and what this call supersedes, serial_ok off, then the
+// validation and the constant uploads (batch_begin).
+static int batch_enter(const Frames& fr, const Entry& e, Batch& b)
+{
+    const rt_compute* scrs = fr.scrs;
+    const int n = fr.n;
+    if (int rc = devices_enter(fr)) return rc;
+    if (fr.cams && scrs && n >= 1 && n <= RT_MAX_BATCH && scrs[0] && scrs[0]->dev) {
         // a pending ahead prepass writes these frames' CameraResults: it comes before anything this
         // call queues, the constant uploads of batch_begin included (they rewrite the block the
         // side-stream prepass reads)
@@ -1795,65 +1755,119 @@ static int terrain_render_batch(const rt_compute* cams, const rt_compute* scrs, 
         for (int f = 0; f < n; ++f)
             if (scrs[f] && scrs[f]->dev && ahead_wait(scrs[f]->dev, lead->stream) != 0)
                 return fail(RT_ERR_HIP, "waiting for the ahead prepass failed");
-        // a full render prepasses in line: the lead's pending ahead prepass is superseded
-        if (lead->ahead_pending && phases != PH_PRE && phases != PH_STAGE) lead->ahead_pending = false;
-        if ((phases & PH_PRE) && lead->fuse_state != rt_device_s::FUSE_NONE) { // so is a staged / fused one
+        // a trace whose frames were not prepassed ahead prepasses in line: the lead's pending ahead prepass
+        // is superseded (rt_terrain_trace_ahead took it before, where it applies)
+        if (lead->ahead_pending && e.trace) lead->ahead_pending = false;
+        if (e.prepass && lead->fuse_state != rt_device_s::FUSE_NONE) { // so is a staged / fused one
             fuse_forget(lead);
             lead->fuse_state = rt_device_s::FUSE_NONE;
         }
     }
     for (int f = 0; scrs && f < n && f < RT_MAX_BATCH; ++f) // rt_terrain_render re-arms its own renders
         if (scrs[f] && scrs[f]->dev) scrs[f]->dev->serial_ok = false;
-    int rc;
+    return batch_begin(fr, b, !e.keep_consts && (e.prepass || !e.trace), !e.keep_consts && e.trace);
+}
+
+// rt_terrain_prepass_ahead, fused: upload the frames' camerarays constants and the frame table a fusing
+// k_trace reads, launch nothing.
+static int batch_stage(const Frames& fr)
+{
     Batch b;
-    const bool keep = (phases & PH_KEEP) != 0;
-    phases &= ~PH_KEEP;
-    if ((rc = batch_begin(cams, scrs, n, b, !keep && (phases & (PH_PRE | PH_STAGE)) != 0, !keep && (phases & PH_TRACE) != 0)))
-        return rc;
-    rt_device dev = b.dev;
-    FrameTable& ft = b.ft;
-    if (count < 0) count = n;
+    if (int rc = batch_enter(fr, Entry{}, b)) return rc;
+    if (int rc = upload_frames(b.dev, b.dev->fuse_table, b.ft)) return rc;
+    return batch_end(b);
+}
+
+// The camerarays prepass of the frames [first, first + count) in one launch, on its own frame table.
+static int batch_prepass(const Frames& fr, const PrepassOpts& o)
+{
+    Batch b;
+    Entry e;
+    e.prepass = true;
+    if (int rc = batch_enter(fr, e, b)) return rc;
+    const int n = fr.n, first = o.first, count = o.count < 0 ? n : o.count;
     // an empty range is valid anywhere: a rank past the last frame of a split prepass (B < N * chunk)
     if (count > n || (count > 0 && (first < 0 || first > n - count))) return fail(RT_ERR_INVALID, "bad prepass frame range");
-    const bool graphs = (dev->flags & RT_DEVICE_GRAPH) && dev->stream != nullptr && phases == (PH_PRE | PH_TRACE);
+    if (count == 0) return batch_end(b);
+    rt_device dev = b.dev;
+    RtLaunch la_cam = make_launch(dev, fr.cams[0]->shader);
+    FrameTable sub{};
+    for (int i = 0; i < count; ++i) {
+        sub.k[i] = b.ft.k[first + i];
+        sub.kcam[i] = b.ft.kcam[first + i];
+        sub.cam[i] = o.camera_out ? o.camera_out + (size_t)(first + i) * 1024 : b.ft.cam[first + i];
+    }
+    if (int rc = upload_frames(dev, dev->pre_table, sub)) return rc;
+    la_cam.frames = dev->pre_table.d;
+    la_cam.frames_host = sub;
+    la_cam.n_frames = (uint32_t)count;
+    rt_launch_camerarays_batch(la_cam);
+    return batch_end(b);
+}
+
+// The trace launch's fields that follow from the shader, the device and the frames' outputs alone.
+static void trace_launch_fields(RtLaunch& a, const Shader* s, const rt_device_s* dev, const FrameTable& ft, int n)
+{
+    // setTargetDepths runs at the start of the tracescreen launch (k_order), from the CameraResults
+    a.cells_from_cam = 1;
+    bool rgba8 = true;
+    for (int f = 0; f < n; ++f) rgba8 = rgba8 && ft.out32[f] == nullptr;
+    // one sample per pixel, at most one AO ray and no float output: hit pixels finish where their last
+    // ray ends (k_trace), not through a per-sample colour and k_finish (DESIGN.md section 5.3)
+    a.fit = s->aa == 1 && s->ao <= 1 && rgba8;
+    // (the colour pool packs frame << 23 | pixel: frames of < 2^23 pixels)
+    a.fitm = s->aa == 1 && s->ao >= 2 && rgba8 && (size_t)dev->width * (size_t)dev->height < ((size_t)1 << 23);
+}
+
+// the camera feed: Flyby's view of frame 0, on the host as soon as the prepass is done
+static int feed_copy(rt_compute cam, const float4* results, hipStream_t s)
+{
+    if (!cam->feed_host) HIP_TRY(hipHostMalloc(&cam->feed_host, 1024 * sizeof(float4)));
+    if (int rc = ensure_event(cam->feed_ev)) return rc;
+    HIP_TRY(hipMemcpyAsync(cam->feed_host, results, 1024 * sizeof(float4), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipEventRecord(cam->feed_ev, s));
+    cam->feed_pending = true;
+    return RT_OK;
+}
+
+// Terrain::render (Terrain.cpp:105-136) for n frames at once: with o.prepass every frame's prepass in one
+// launch, then setTargetDepths and one tracescreen over all frames' units (frame-major), on frame 0's
+// device stream and buffers.  Frames on other devices (a FrameRing's slots) are ordered around the batch
+// with events.
+static int batch_trace(const Frames& fr, const TraceOpts& o)
+{
+    const Shard shard = o.shard;
+    if (shard.count < 1 || shard.rank < 0 || shard.rank >= shard.count) return fail(RT_ERR_INVALID, "bad shard");
+    if (o.feed && fr.n != 1) return fail(RT_ERR_INVALID, "the camera feed is per frame");
+    int rc;
+    Batch b;
+    Entry e;
+    e.prepass = o.prepass;
+    e.trace = true;
+    e.keep_consts = o.keep_consts;
+    if ((rc = batch_enter(fr, e, b))) return rc;
+    const rt_compute *cams = fr.cams, *scrs = fr.scrs;
+    const int n = fr.n;
+    rt_device dev = b.dev;
+    FrameTable& ft = b.ft;
+    const bool graphs = (dev->flags & RT_DEVICE_GRAPH) && dev->stream != nullptr && o.prepass;
     // gathered prepass results: the table reads them, and each frame's CameraResults array
     // receives its copy (Terrain::getCameraView stays valid) once the trace is queued, so the
     // copies do not delay it
     float4* cam_copy[RT_MAX_BATCH] = {};
-    if (camera_in) {
+    if (o.camera_in) {
         for (int f = 0; f < n; ++f) {
-            const float4* src = camera_in + (size_t)f * 1024;
+            const float4* src = o.camera_in + (size_t)f * 1024;
             if (ft.cam[f] != scrs[f]->dev->scratch_cam) cam_copy[f] = ft.cam[f];
             ft.cam[f] = const_cast<float4*>(src);
         }
     }
-    if (phases == PH_STAGE) { // the frames' camerarays constants (above) and the table a fusing k_trace reads
-        if ((rc = upload_frames(dev, dev->fuse_table, ft))) return rc;
-        return batch_end(scrs, n, b);
-    }
-    if (phases == PH_PRE) {
-        // the prepass of frames [first, first + count) only, on its own table
-        if (count == 0) return batch_end(scrs, n, b);
-        RtLaunch la_cam = make_launch(dev, cams[0]->shader);
-        FrameTable sub{};
-        for (int i = 0; i < count; ++i) {
-            sub.k[i] = ft.k[first + i];
-            sub.kcam[i] = ft.kcam[first + i];
-            sub.cam[i] = camera_out ? camera_out + (size_t)(first + i) * 1024 : ft.cam[first + i];
-        }
-        if ((rc = upload_frames(dev, dev->pre_table, sub))) return rc;
-        la_cam.frames = dev->pre_table.d;
-        la_cam.frames_host = sub;
-        la_cam.n_frames = (uint32_t)count;
-        rt_launch_camerarays_batch(la_cam);
-        return batch_end(scrs, n, b);
-    }
     if ((rc = ensure_split_buffers(dev, b.s0->aa, b.s0->ao, n))) return rc;
     RtLaunch la_cam = make_launch(dev, cams[0]->shader), la_scr = make_launch(dev, scrs[0]->shader);
-    if (packed_dst) { // rt_terrain_render_batch_packed: frame f's shard pixels straight into its packed buffer
+    if (o.packed_dst) {
         for (int f = 0; f < n; ++f) {
             if (ft.out32[f]) return fail(RT_ERR_UNSUPPORTED, "packed output: RGBA8-only devices (no RT_DEVICE_FLOAT_OUTPUT)");
-            ft.out8[f] = reinterpret_cast<uint32_t*>(packed_dst + (size_t)f * packed_stride);
+            ft.out8[f] = reinterpret_cast<uint32_t*>(o.packed_dst + (size_t)f * o.packed_stride);
         }
         la_scr.packed = 1;
     }
@@ -1863,8 +1877,7 @@ static int terrain_render_batch(const rt_compute* cams, const rt_compute* scrs, 
     // (the prepass rays march 2-3x slower beside the units), so off by default.  Not for the instrumented
     // kernels (their prepass counts stay separate), the camera feed (it wants the CameraResults before the
     // trace), a trace from gathered CameraResults or a fused prepass.
-    const bool gated = phases == (PH_PRE | PH_TRACE) && !feed && !camera_in &&
-                       (!fuse || (fuse->wait_ctl == nullptr && fuse->next.ctl == nullptr)) &&
+    const bool gated = o.prepass && !o.feed && !o.camera_in && o.fuse.wait_ctl == nullptr && o.fuse.next.ctl == nullptr &&
                        b.s0->landscape == RT_NOMADPLAINS &&
                        (dev->flags & RT_DEVICE_GATED) && !(dev->flags & RT_DEVICE_STATS);
     if (gated)
@@ -1880,31 +1893,20 @@ static int terrain_render_batch(const rt_compute* cams, const rt_compute* scrs, 
     la_cam.frames = la_scr.frames = dev->table.d;
     la_cam.frames_host = la_scr.frames_host = ft;
     la_cam.n_frames = la_scr.n_frames = (uint32_t)n;
-    // setTargetDepths runs at the start of the tracescreen launch (k_order), from the CameraResults; the
-    // gated launch's k_order orders the units by the frames' previous CellDistance instead (scheduling
+    trace_launch_fields(la_scr, b.s0, dev, ft, n);
+    // the gated launch's k_order orders the units by the frames' previous CellDistance instead (scheduling
     // only: each unit derives its cells' brackets from this frame's rays, and the frame's last prepass
     // task writes its CellDistance)
-    la_scr.cells_from_cam = gated ? 0 : 1;
-    if (fuse) {
-        la_scr.fuse_next = fuse->next;
-        la_scr.after_order_fuse = fuse->next_after_order;
-        la_scr.wait_ctl = fuse->wait_ctl;
-        la_scr.wait_total = fuse->wait_total;
-    }
-    // one sample per pixel, at most one AO ray and no float output: hit pixels finish where their last
-    // ray ends (k_trace), not through a per-sample colour and k_finish (DESIGN.md section 5.3)
-    la_scr.fit = b.s0->aa == 1 && b.s0->ao <= 1;
-    // (the colour pool packs frame << 23 | pixel: frames of < 2^23 pixels)
-    la_scr.fitm = b.s0->aa == 1 && b.s0->ao >= 2 && (size_t)dev->width * (size_t)dev->height < ((size_t)1 << 23);
-    for (int f = 0; f < n; ++f) {
-        la_scr.fit = la_scr.fit && ft.out32[f] == nullptr;
-        la_scr.fitm = la_scr.fitm && ft.out32[f] == nullptr;
-    }
+    if (gated) la_scr.cells_from_cam = 0;
+    la_scr.fuse_next = o.fuse.next;
+    la_scr.after_order_fuse = o.fuse.next_after_order;
+    la_scr.wait_ctl = o.fuse.wait_ctl;
+    la_scr.wait_total = o.fuse.wait_total;
     auto pre = [&] {
-        if ((phases & PH_PRE) && !gated) rt_launch_camerarays_batch(la_cam);
+        if (o.prepass && !gated) rt_launch_camerarays_batch(la_cam);
     };
     if (gated) ++dev->gated_launches;
-    else if (phases & PH_PRE) ++dev->prepass_launches;
+    else if (o.prepass) ++dev->prepass_launches;
     if (graphs && !gated) {
         // the constant / table uploads stay outside: they precede the replay on this stream
         std::vector<uint64_t> kp;
@@ -1914,18 +1916,10 @@ static int terrain_render_batch(const rt_compute* cams, const rt_compute* scrs, 
     } else {
         pre();
     }
-    if (feed) {
-        // Flyby's view of this frame, on the host as soon as the prepass is done
-        rt_compute cam = cams[0];
-        if (!cam->feed_host) HIP_TRY(hipHostMalloc(&cam->feed_host, 1024 * sizeof(float4)));
-        if (!cam->feed_ev) HIP_TRY(hipEventCreateWithFlags(&cam->feed_ev, hipEventDisableTiming));
-        HIP_TRY(hipMemcpyAsync(cam->feed_host, ft.cam[0], 1024 * sizeof(float4), hipMemcpyDeviceToHost, dev->stream));
-        HIP_TRY(hipEventRecord(cam->feed_ev, dev->stream));
-        cam->feed_pending = true;
-    }
+    if (o.feed && (rc = feed_copy(cams[0], ft.cam[0], dev->stream))) return rc;
     auto trace = [&] {
-        rt_launch_tracescreen(la_scr, 0, 0, (uint32_t)dev->width, (uint32_t)dev->height, (uint32_t)shard_rank,
-                              (uint32_t)shard_count);
+        rt_launch_tracescreen(la_scr, 0, 0, (uint32_t)dev->width, (uint32_t)dev->height, (uint32_t)shard.rank,
+                              (uint32_t)shard.count);
     };
     {
         KernelTimer kt(dev);
@@ -1933,8 +1927,8 @@ static int terrain_render_batch(const rt_compute* cams, const rt_compute* scrs, 
             std::vector<uint64_t> kt_key;
             key_launch(kt_key, la_scr);
             key_frames(kt_key, ft);
-            const uint64_t extra[] = {(uint64_t)dev->width, (uint64_t)dev->height, (uint64_t)shard_rank,
-                                      (uint64_t)shard_count};
+            const uint64_t extra[] = {(uint64_t)dev->width, (uint64_t)dev->height, (uint64_t)shard.rank,
+                                      (uint64_t)shard.count};
             kt_key.insert(kt_key.end(), std::begin(extra), std::end(extra));
             if ((rc = graph_run(dev, dev->graph_trace, std::move(kt_key), trace))) return rc;
         } else {
@@ -1947,30 +1941,47 @@ static int terrain_render_batch(const rt_compute* cams, const rt_compute* scrs, 
     }
     for (int f = 0; f < n; ++f)
         if (cam_copy[f])
-            HIP_TRY(hipMemcpyAsync(cam_copy[f], camera_in + (size_t)f * 1024, 1024 * sizeof(float4),
+            HIP_TRY(hipMemcpyAsync(cam_copy[f], o.camera_in + (size_t)f * 1024, 1024 * sizeof(float4),
                                    hipMemcpyDeviceToDevice, dev->stream));
-    return batch_end(scrs, n, b);
+    return batch_end(b);
+}
+
+// Terrain::render for the frames (rt_terrain_render_batch): the prepass in line, then the trace
+static int batch_render(const Frames& fr, Shard shard)
+{
+    TraceOpts o;
+    o.prepass = true;
+    o.shard = shard;
+    return batch_trace(fr, o);
 }
 
 int rt_terrain_render_batch(const rt_compute* cams, const rt_compute* scrs, int n, int shard_rank, int shard_count)
 {
-    return terrain_render_batch(cams, scrs, n, shard_rank, shard_count, false);
+    return batch_render(Frames{cams, scrs, n}, Shard{shard_rank, shard_count});
 }
 
-// RT_DEVICE_DEFERRED: launch the device's pending frame (its setTargetDepths + trace; its prepass and constant
-// blocks are queued already) with nothing fused.  Every call that launches on, reads or reconfigures the
-// device calls this first.
 static int defer_flush_batch(rt_device d);
-static int deferred_render_batch(rt_device d, rt_compute cam, rt_compute scr);
+static int deferred_queue(rt_device d, rt_compute cam, rt_compute scr);
 
-static int defer_flush_one(rt_device d)
+// RT_DEVICE_DEFERRED: launch the device's pending frame (its setTargetDepths + trace; its prepass and constant
+// blocks are queued already), with the next frame's prepass in `fuse` or nothing fused.
+static int defer_trace(rt_device d, const TraceFuse& fuse)
 {
-    if (!d->defer.pending) return RT_OK;
     const rt_device_s::Deferred p = d->defer;
     d->defer.pending = false;
-    const int rc = terrain_render_batch(&p.cam, &p.scr, 1, p.rank, p.count, false, PH_TRACE | PH_KEEP);
+    TraceOpts o;
+    o.keep_consts = true;
+    o.fuse = fuse;
+    o.shard = Shard{p.rank, p.count};
+    const int rc = batch_trace(Frames{&p.cam, &p.scr, 1}, o);
     captures_launch(d, RING_FRAME_DEFER, d->fb8, rc); // the frame's captures right behind its trace
     return rc;
+}
+
+// Every call that launches on, reads or reconfigures the device calls defer_flush first.
+static int defer_flush_one(rt_device d)
+{
+    return d->defer.pending ? defer_trace(d, TraceFuse{}) : RT_OK;
 }
 
 static int defer_flush(rt_device d)
@@ -1978,6 +1989,109 @@ static int defer_flush(rt_device d)
     if (!d) return RT_OK;
     if (!d->dq.empty()) return defer_flush_batch(d); // (a device has frames queued one way or the other, not both)
     return defer_flush_one(d);
+}
+
+// These devices upload and launch on stream s until the scope ends.
+struct StreamRedirect {
+    rt_device devs[RT_MAX_BATCH];
+    hipStream_t was[RT_MAX_BATCH];
+    int n = 0;
+    StreamRedirect(const rt_device* ds, int count, hipStream_t s)
+    {
+        for (; n < count && n < RT_MAX_BATCH; ++n) {
+            devs[n] = ds[n];
+            was[n] = ds[n]->stream;
+            ds[n]->stream = s;
+        }
+    }
+    ~StreamRedirect()
+    {
+        for (int i = 0; i < n; ++i) devs[i]->stream = was[i];
+    }
+};
+
+// Terrain::render (Terrain.cpp:105-136), one frame per call on the device's stream.  Frame i+1's
+// camerarays prepass needs only frame i's k_order to be done (the last reader of CameraResults): on the
+// device's own prepass stream it waits for that k_order (ev_order, recorded between k_order and k_trace)
+// and so runs in frame i's trace tail, where the persistent k_trace's blocks retire, instead of after
+// the whole frame; the trace waits for it (ev_pre).  Same launches, same bits.  The first frame, and a
+// frame after anything else read this device's CameraResults on its stream (a feed render, an ahead or
+// fused prepass, a batch), prepass in line; so do the instrumented, graph and gated devices
+// (rt_render_route.h has the rules).
+// route: FULL_INLINE, SERIAL_FIRST or SERIAL_PRESTREAM (rtr::serial_route)
+static int serial_render(rt_device d, const Frames& fr, Shard shard, rtr::Route route)
+{
+    if (route == rtr::FULL_INLINE) {
+        if (d) d->serial_ok = false;
+        return batch_render(fr, shard);
+    }
+    if (int rc0 = host_flag_check(d)) return rc0;
+    HIP_TRY(hipSetDevice(d->ordinal));
+    if (int rc = ensure_event(d->ev_order)) return rc;
+    if (route == rtr::SERIAL_FIRST) {
+        int rc = batch_render(fr, shard); // records ev_order
+        d->serial_ok = rc == RT_OK;
+        return rc;
+    }
+    if (!d->pre_stream) HIP_TRY(hipStreamCreateWithFlags(&d->pre_stream, hipStreamNonBlocking));
+    if (int rc = ensure_event(d->ev_pre)) return rc;
+    HIP_TRY(hipStreamWaitEvent(d->pre_stream, d->ev_order, 0));
+    int rc;
+    {
+        StreamRedirect on_pre(&d, 1, d->pre_stream); // the prepass uploads the camerarays constants and launches there
+        rc = batch_prepass(fr, PrepassOpts{});
+    }
+    if (rc) {
+        d->serial_ok = false;
+        return rc;
+    }
+    HIP_TRY(hipEventRecord(d->ev_pre, d->pre_stream));
+    HIP_TRY(hipStreamWaitEvent(d->stream, d->ev_pre, 0));
+    TraceOpts o;
+    o.shard = shard;
+    rc = batch_trace(fr, o);
+    d->serial_ok = rc == RT_OK;
+    if (rc == RT_OK) { // a render with a prepass launch (rt_device_info), on the prepass stream
+        ++d->prepass_launches;
+        ++d->prestream_renders;
+    }
+    return rc;
+}
+
+static bool tables_match(const Shader* a, const Shader* b) // (same_tables, false without shaders or textures)
+{
+    return a && b && a->textures[0] && b->textures[0] && same_tables(a, b);
+}
+
+// what rt_render_route.h decides an rt_terrain_render call's route by, as it is now
+static rtr::State route_state(rt_device d, rt_compute cam, rt_compute scr, int shard_count)
+{
+    rtr::State s;
+    if (!d) return s;
+    s.flags = d->flags;
+    s.has_stream = d->stream != nullptr;
+    s.ahead_pending = d->ahead_pending;
+    s.ahead_in_pending = d->ahead_in_pending;
+    s.fuse_active = d->fuse_state != rt_device_s::FUSE_NONE;
+    s.serial_ok = d->serial_ok;
+    s.order_recorded = d->order_recorded;
+    if (!(d->flags & RT_DEVICE_DEFERRED)) return s; // (the rest is read for such a device only)
+    s.defer_k = d->defer_k;
+    s.shard_count = shard_count;
+    s.pixels = (size_t)d->width * (size_t)d->height;
+    s.cam_nomadplains = cam->shader && cam->shader->landscape == RT_NOMADPLAINS;
+    s.scr_nomadplains = scr->shader && scr->shader->landscape == RT_NOMADPLAINS;
+    s.tables_equal = tables_match(cam->shader, scr->shader);
+    const rt_device_s::Deferred& p = d->defer;
+    if (p.pending) {
+        const Shader* ps = p.scr->shader;
+        s.prev.pending = true;
+        s.prev.nomadplains = ps && ps->landscape == RT_NOMADPLAINS;
+        s.prev.grad_dirty = ps && ps->grad_dirty;
+        s.prev.tables_equal = tables_match(cam->shader, ps);
+        s.prev.rank_in_frame = (size_t)p.rank < rt_shard_tiles(d->width, d->height, 0, 1);
+    }
+    return s;
 }
 
 // rt_terrain_render on an RT_DEVICE_DEFERRED device (Terrain.cpp:105-136, one frame per call).  The frame's
@@ -1990,46 +2104,38 @@ static int defer_flush(rt_device d)
 //   writes CameraResults; reads only frame i's tracescreen constants] [tracescreen constants of frame i+1]
 // (the prepass kernels are the only readers of the camerarays block).  Anything else falls back to a flush
 // and the full render.
-static int deferred_render(rt_device d, rt_compute cam, rt_compute scr, int shard_rank, int shard_count)
+// route: FULL_INLINE or one of DEFER_* (rtr::route)
+static int deferred_render(rt_device d, const Frames& fr, Shard shard, rtr::Route route)
 {
-    if (shard_count < 1 || shard_rank < 0 || shard_rank >= shard_count) return fail(RT_ERR_INVALID, "bad shard");
-    const bool np = cam->shader && scr->shader && cam->shader->landscape == RT_NOMADPLAINS &&
-                    scr->shader->landscape == RT_NOMADPLAINS;
-    const bool plain = np && d->stream && !(d->flags & (RT_DEVICE_GRAPH | RT_DEVICE_STATS | RT_DEVICE_GATED)) &&
-                       !d->ahead_pending && !d->ahead_in_pending && d->fuse_state == rt_device_s::FUSE_NONE;
-    if (!plain) {
+    const rt_compute cam = fr.cams[0], scr = fr.scrs[0];
+    if (shard.count < 1 || shard.rank < 0 || shard.rank >= shard.count) return fail(RT_ERR_INVALID, "bad shard");
+    if (route == rtr::FULL_INLINE) {
         if (int rc = defer_flush(d)) return rc;
-        return terrain_render_batch(&cam, &scr, 1, shard_rank, shard_count, false);
+        return batch_render(fr, shard);
     }
     if (int rc0 = host_flag_check(d)) return rc0;
     HIP_TRY(hipSetDevice(d->ordinal));
-    if (d->defer_k >= 2 && shard_count == 1 && same_tables(cam->shader, scr->shader)) {
+    if (route == rtr::DEFER_QUEUE) {
         if (int rc = defer_flush_one(d)) return rc; // (a K = 1 frame pending: traced alone first)
-        return deferred_render_batch(d, cam, scr);
+        return deferred_queue(d, cam, scr);
     }
-    if (int rc = defer_flush_batch(d)) return rc; // (frames queued for a batch, then a sharded render: they go first)
-    if ((size_t)d->width * (size_t)d->height < RT_DEFER_FUSE_MIN_PIXELS && !(d->flags & RT_DEVICE_DEBUG_DEFER_SMALL)) {
-        // a small frame's trace is shorter than the prepass it would carry (profiles/r06/deferred.md): it renders
-        // as without the flag, its prepass on the prepass stream in the previous frame's trace tail
+    // frames queued for a batch, then a sharded render: they go first.  (The route holds behind this flush: with
+    // frames queued no frame is pending, before it or after, and nothing else of the state changes.)
+    if (int rc = defer_flush_batch(d)) return rc;
+    if (route == rtr::DEFER_SMALL) {
+        // it renders as without the flag, its prepass on the prepass stream in the previous frame's trace tail
         if (int rc = defer_flush(d)) return rc;
-        return serial_render(d, cam, scr, shard_rank, shard_count);
+        // the state behind the flush: a trace it launched turned serial_ok off, so this frame prepasses in line
+        return serial_render(d, fr, shard, rtr::serial_route(route_state(d, cam, scr, shard.count)));
     }
-    const rt_device_s::Deferred p = d->defer;
-    // the pending frame's trace must run a k_trace (a single frame's shard past the last tile launches none)
-    // with the noise tables this prepass reads
-    // (the trace loads its noise tables from the pending frame's tracescreen gradients, which are up to date on the
-    // device unless a later write dirtied them)
-    const bool fuse = p.pending && p.scr->shader && p.scr->shader->landscape == RT_NOMADPLAINS &&
-                      !p.scr->shader->grad_dirty && same_tables(cam->shader, p.scr->shader) &&
-                      (size_t)p.rank < rt_shard_tiles(d->width, d->height, 0, 1);
-    if (!fuse) {
+    if (route == rtr::DEFER_INLINE) {
         if (int rc = defer_flush(d)) return rc;
         // this frame's prepass in line (its camerarays constants go up with it)
-        if (int rc = terrain_render_batch(&cam, &scr, 1, 0, 1, false, PH_PRE)) return rc;
+        if (int rc = batch_prepass(fr, PrepassOpts{})) return rc;
         ++d->prepass_launches; // (a render with a prepass launch, rt_device_info)
-    } else {
+    } else { // DEFER_FUSE
         Batch b; // this frame's camerarays constants (only the prepass kernels read that block)
-        if (int rc = batch_begin(&cam, &scr, 1, b, true, false)) return rc;
+        if (int rc = batch_begin(fr, b, true, false)) return rc;
         FrameTable sub{};
         sub.k[0] = b.ft.k[0];
         sub.kcam[0] = b.ft.kcam[0];
@@ -2037,16 +2143,41 @@ static int deferred_render(rt_device d, rt_compute cam, rt_compute scr, int shar
         if (int rc = upload_frames(d, d->fuse_table, sub)) return rc;
         TraceFuse tf;
         tf.next = FusedPrepass{d->fuse_table.d, d->fctl, (uint32_t)RT_FUSE_TASKS_PER_FRAME};
-        d->defer.pending = false;
-        const int rc = terrain_render_batch(&p.cam, &p.scr, 1, p.rank, p.count, false, PH_TRACE | PH_KEEP, 0, -1,
-                                            nullptr, nullptr, &tf);
-        captures_launch(d, RING_FRAME_DEFER, d->fb8, rc); // the pending frame's captures right behind its trace
-        if (rc) return rc;
+        if (int rc = defer_trace(d, tf)) return rc;
         ++d->deferred_fused;
     }
     // this frame's tracescreen constants (and noise gradients), behind the trace that read the previous frame's
     if (int rc = sync_shader(d, scr->shader)) return rc;
-    d->defer = rt_device_s::Deferred{cam, scr, shard_rank, shard_count, true};
+    d->defer = rt_device_s::Deferred{cam, scr, shard.rank, shard.count, true};
+    return RT_OK;
+}
+
+int rt_terrain_render(rt_compute cam, rt_compute scr, int shard_rank, int shard_count)
+{
+    rt_device d = (cam && scr && scr->dev && cam->dev == scr->dev) ? scr->dev : nullptr;
+    const rtr::Route route = rtr::route(route_state(d, cam, scr, shard_count));
+    const Frames fr{&cam, &scr, 1};
+    const Shard shard{shard_rank, shard_count};
+    if (d && (d->flags & RT_DEVICE_DEFERRED)) return deferred_render(d, fr, shard, route);
+    return serial_render(d, fr, shard, route);
+}
+
+int rt_terrain_render_feed(rt_compute cam, rt_compute scr, int shard_rank, int shard_count)
+{
+    if (cam && cam->dev) cam->dev->serial_ok = false; // its CameraResults copy follows the prepass
+    TraceOpts o;
+    o.prepass = o.feed = true;
+    o.shard = Shard{shard_rank, shard_count};
+    return batch_trace(Frames{&cam, &scr, 1}, o);
+}
+
+int rt_terrain_feed_wait(rt_compute cam, float* camera_results)
+{
+    if (!cam || !camera_results) return fail(RT_ERR_INVALID, "bad arguments");
+    if (!cam->feed_pending) return fail(RT_ERR_STATE, "no camera feed pending (rt_terrain_render_feed)");
+    HIP_TRY(hipEventSynchronize(cam->feed_ev));
+    memcpy(camera_results, cam->feed_host, 1024 * sizeof(float4));
+    cam->feed_pending = false;
     return RT_OK;
 }
 
@@ -2057,11 +2188,18 @@ static int slot_get(rt_device d, int i, rt_device_s::FrameSlot** out)
     while ((int)d->slots.size() <= i) d->slots.emplace_back(new rt_device_s::FrameSlot());
     rt_device_s::FrameSlot& f = *d->slots[i];
     if (!f.cam) {
+        // into a slot of its own, published only when it is whole (its destructor frees a partial one): a
+        // failed hipMalloc leaves f empty, and the next call allocates again
+        rt_device_s::FrameSlot made;
         const size_t px = (size_t)d->width * d->height;
-        HIP_TRY(hipMalloc(&f.cam, 1024 * sizeof(float4)));
-        HIP_TRY(hipMalloc(&f.cells, 1024 * sizeof(float2)));
-        HIP_TRY(hipMalloc(&f.fb8, px * 4));
-        if (d->fb32) HIP_TRY(hipMalloc(&f.fb32, px * 16));
+        HIP_TRY(hipMalloc(&made.cam, 1024 * sizeof(float4)));
+        HIP_TRY(hipMalloc(&made.cells, 1024 * sizeof(float2)));
+        HIP_TRY(hipMalloc(&made.fb8, px * 4));
+        if (d->fb32) HIP_TRY(hipMalloc(&made.fb32, px * 16));
+        std::swap(f.cam, made.cam);
+        std::swap(f.cells, made.cells);
+        std::swap(f.fb8, made.fb8);
+        std::swap(f.fb32, made.fb32);
     }
     *out = &f;
     return RT_OK;
@@ -2095,7 +2233,7 @@ static int block_upload(rt_device d, rt_device_s::LaunchBlock& hb, int from, int
 // the same stream: the next launch's k_order comes after this whole kernel).  last: the n-th frame is the
 // flush's last, so it writes the device's framebuffers and the API's CellDistance; its CameraResults are
 // copied to the API's array behind the trace.
-static int batch_trace(rt_device d, int n, int m, bool last)
+static int dq_trace(rt_device d, int n, int m, bool last)
 {
     rt_compute cam = d->dq_cam, scr = d->dq_scr;
     Shader* s = scr->shader;
@@ -2119,14 +2257,11 @@ static int batch_trace(rt_device d, int n, int m, bool last)
     a.frames = &db->ft;
     a.frames_host = ft;
     a.n_frames = (uint32_t)n;
-    a.cells_from_cam = 1;
+    trace_launch_fields(a, s, d, ft, n);
     if (m > 0) {
         a.fuse_next = FusedPrepass{&db->nx, d->fctl, (uint32_t)m * (uint32_t)RT_FUSE_TASKS_PER_FRAME};
         d->deferred_fused += (unsigned long long)m;
     }
-    // (as terrain_render_batch: hit pixels finish in k_trace with one sample, <= 1 AO ray and no float output)
-    a.fit = s->aa == 1 && s->ao <= 1 && !d->fb32;
-    a.fitm = s->aa == 1 && s->ao >= 2 && !d->fb32 && (size_t)d->width * (size_t)d->height < ((size_t)1 << 23);
     {
         KernelTimer kt(d);
         rt_launch_tracescreen(a, 0, 0, (uint32_t)d->width, (uint32_t)d->height, 0u, 1u);
@@ -2144,7 +2279,7 @@ static int batch_trace(rt_device d, int n, int m, bool last)
 }
 
 // the standalone prepass of the first n queued frames (nothing queued before them runs a trace to fuse it into)
-static int batch_prepass(rt_device d, int n)
+static int dq_prepass(rt_device d, int n)
 {
     rt_device_s::LaunchBlock hb{};
     rt_device_s::LaunchBlock* db = nullptr;
@@ -2167,9 +2302,9 @@ static int defer_flush_batch(rt_device d)
     const int K = d->defer_k;
     while (!d->dq.empty()) {
         if (d->dq_pre == 0)
-            if (int rc = batch_prepass(d, std::min<int>(K, (int)d->dq.size()))) return rc;
+            if (int rc = dq_prepass(d, std::min<int>(K, (int)d->dq.size()))) return rc;
         const int n = d->dq_pre, m = std::min<int>(K, (int)d->dq.size() - n);
-        if (int rc = batch_trace(d, n, m, (int)d->dq.size() == n)) {
+        if (int rc = dq_trace(d, n, m, (int)d->dq.size() == n)) {
             captures_launch(d, RING_FRAME_ALL, nullptr, rc); // the queued frames are dropped: their captures fail
             d->dq.clear();
             d->dq_pre = 0;
@@ -2183,7 +2318,7 @@ static int defer_flush_batch(rt_device d)
 // its slot); the K-th queued frame beyond a launch-ready group launches that group with this group's prepasses
 // fused.  Slots are reused by stream order: a slot's buffers are next written by launches behind the one that
 // read them.
-static int deferred_render_batch(rt_device d, rt_compute cam, rt_compute scr)
+static int deferred_queue(rt_device d, rt_compute cam, rt_compute scr)
 {
     const int K = d->defer_k;
     Shader *sc = cam->shader, *ss = scr->shader;
@@ -2212,8 +2347,8 @@ static int deferred_render_batch(rt_device d, rt_compute cam, rt_compute scr)
     }
     f->dk = f->dkcam = nullptr;
     d->dq.push_back(slot);
-    if (d->dq_pre == 0 && (int)d->dq.size() == K) return batch_prepass(d, K); // the first group: nothing to ride on
-    if (d->dq_pre == K && (int)d->dq.size() == 2 * K) return batch_trace(d, K, K, false);
+    if (d->dq_pre == 0 && (int)d->dq.size() == K) return dq_prepass(d, K); // the first group: nothing to ride on
+    if (d->dq_pre == K && (int)d->dq.size() == 2 * K) return dq_trace(d, K, K, false);
     return RT_OK;
 }
 
@@ -2231,22 +2366,32 @@ int rt_terrain_render_batch_packed(const rt_compute* cams, const rt_compute* scr
         if (frame_stride < need || frame_stride % 16) return fail(RT_ERR_INVALID, "packed output: frame_stride %zu < %zu bytes "
                                                                    "or not 16-byte aligned", frame_stride, need);
     }
-    return terrain_render_batch(cams, scrs, n, shard_rank, shard_count, false, PH_PRE | PH_TRACE, 0, -1, nullptr,
-                                nullptr, nullptr, (uint8_t*)dst_device, frame_stride);
+    TraceOpts o;
+    o.prepass = true;
+    o.packed_dst = (uint8_t*)dst_device;
+    o.packed_stride = frame_stride;
+    o.shard = Shard{shard_rank, shard_count};
+    return batch_trace(Frames{cams, scrs, n}, o);
 }
 
 int rt_terrain_prepass_batch(const rt_compute* cams, const rt_compute* scrs, int n, int first, int count,
                              void* camera_out)
 {
-    return terrain_render_batch(cams, scrs, n, 0, 1, false, PH_PRE, first, count, (float4*)camera_out);
+    PrepassOpts o;
+    o.first = first;
+    o.count = count;
+    o.camera_out = (float4*)camera_out;
+    return batch_prepass(Frames{cams, scrs, n}, o);
 }
 
 int rt_terrain_trace_batch(const rt_compute* cams, const rt_compute* scrs, int n, int shard_rank, int shard_count,
                            const void* camera_in)
 {
     if (!camera_in) return fail(RT_ERR_INVALID, "camera_in: the batch's gathered CameraResults");
-    return terrain_render_batch(cams, scrs, n, shard_rank, shard_count, false, PH_TRACE, 0, -1, nullptr,
-                                (const float4*)camera_in);
+    TraceOpts o;
+    o.camera_in = (const float4*)camera_in;
+    o.shard = Shard{shard_rank, shard_count};
+    return batch_trace(Frames{cams, scrs, n}, o);
 }
 
 // The prepass one batch ahead.  For nomadplains on uninstrumented devices the
@@ -2263,9 +2408,10 @@ int rt_terrain_prepass_ahead(const rt_compute* cams, const rt_compute* scrs, int
     for (int f = 0; f < n; ++f)
         if (!cams[f] || !scrs[f] || cams[f]->dev != scrs[f]->dev) return fail(RT_ERR_INVALID, "computes must share a device");
     rt_device lead = scrs[0]->dev;
-    if (int rc0 = host_flag_check(lead)) return rc0;
-    for (int f = 0; f < n; ++f)
-        if (int rc0 = defer_flush(scrs[f]->dev)) return rc0;
+    const Frames fr{cams, scrs, n};
+    // (its own order from here: GRAPH is refused behind the flushes, and the side stream is set up before the
+    // entry step of the stage or prepass below runs on it)
+    if (int rc0 = devices_enter(fr)) return rc0;
     if (lead->flags & RT_DEVICE_GRAPH) return fail(RT_ERR_STATE, "the ahead prepass runs on a side stream: not with RT_DEVICE_GRAPH");
     if (lead->ahead_pending) return fail(RT_ERR_STATE, "a prepass is already ahead for this device's batch: trace it first");
     if (lead->fuse_state == rt_device_s::FUSE_FUSED && lead->ev_fuser_done) {
@@ -2277,8 +2423,8 @@ int rt_terrain_prepass_ahead(const rt_compute* cams, const rt_compute* scrs, int
     HIP_TRY(hipSetDevice(lead->ordinal));
     hipStream_t side = ahead_stream(lead->ordinal, true);
     if (!side) return fail(RT_ERR_HIP, "side stream");
-    if (!lead->ev_order) HIP_TRY(hipEventCreateWithFlags(&lead->ev_order, hipEventDisableTiming));
-    if (!lead->ev_ahead) HIP_TRY(hipEventCreateWithFlags(&lead->ev_ahead, hipEventDisableTiming));
+    if (int rc = ensure_event(lead->ev_order)) return rc;
+    if (int rc = ensure_event(lead->ev_ahead)) return rc;
     // before the first recorded k_order: after everything queued so far
     if (!lead->order_recorded) {
         HIP_TRY(hipEventRecord(lead->ev_order, lead->stream));
@@ -2287,27 +2433,23 @@ int rt_terrain_prepass_ahead(const rt_compute* cams, const rt_compute* scrs, int
     HIP_TRY(hipStreamWaitEvent(side, lead->ev_order, 0));
     const Shader* s0 = scrs[0]->shader;
     const bool fuse = s0 && s0->landscape == RT_NOMADPLAINS && !(lead->flags & RT_DEVICE_STATS);
-    // the batch's devices upload their constants and launch on the side stream for this call
-    std::vector<std::pair<rt_device, hipStream_t>> saved;
-    for (int f = 0; f < n; ++f) {
-        rt_device d = scrs[f]->dev;
-        bool seen = false;
-        for (auto& p : saved) seen |= p.first == d;
-        if (!seen) {
-            saved.emplace_back(d, d->stream);
-            d->stream = side;
-        }
+    rt_device devs[RT_MAX_BATCH]; // the batch's devices, each once
+    int n_devs = 0;
+    for (int f = 0; f < n; ++f)
+        if (std::find(devs, devs + n_devs, scrs[f]->dev) == devs + n_devs) devs[n_devs++] = scrs[f]->dev;
+    int rc;
+    {
+        StreamRedirect on_side(devs, n_devs, side); // they upload their constants and launch there for this call
+        rc = fuse ? batch_stage(fr) : batch_prepass(fr, PrepassOpts{});
     }
-    int rc = terrain_render_batch(cams, scrs, n, 0, 1, false, fuse ? PH_STAGE : PH_PRE, 0, n, nullptr);
-    for (auto& p : saved) p.first->stream = p.second;
     if (rc) return rc;
     HIP_TRY(hipEventRecord(lead->ev_ahead, side));
     lead->ahead_pending = true;
     lead->ahead_cams.assign(cams, cams + n);
     lead->fuse_devs.clear();
-    for (auto& p : saved) { // every device whose frames it writes or stages (not the lead alone)
-        rt_device d = p.first;
-        if (!d->ev_ahead_in) HIP_TRY(hipEventCreateWithFlags(&d->ev_ahead_in, hipEventDisableTiming));
+    for (int i = 0; i < n_devs; ++i) { // every device whose frames it writes or stages (not the lead alone)
+        rt_device d = devs[i];
+        if (int rc = ensure_event(d->ev_ahead_in)) return rc;
         HIP_TRY(hipEventRecord(d->ev_ahead_in, side));
         d->ahead_in_pending = true;
         lead->fuse_devs.push_back(d);
@@ -2330,16 +2472,16 @@ int rt_terrain_trace_ahead(const rt_compute* cams, const rt_compute* scrs, int n
 {
     if (!cams || !scrs || n < 1 || n > RT_MAX_BATCH || !scrs[0] || !scrs[0]->shader) return fail(RT_ERR_INVALID, "a batch holds 1..%d frames", RT_MAX_BATCH);
     rt_device lead = scrs[0]->dev;
-    if (int rc0 = host_flag_check(lead)) return rc0;
-    for (int f = 0; f < n; ++f)
-        if (scrs[f] && scrs[f]->dev)
-            if (int rc0 = defer_flush(scrs[f]->dev)) return rc0;
+    const Frames fr{cams, scrs, n};
+    if (int rc0 = devices_enter(fr)) return rc0; // (before the trace's entry step: what follows reads the flushed state)
     HIP_TRY(hipSetDevice(lead->ordinal));
     bool ahead = lead->ahead_pending && (size_t)n <= lead->ahead_cams.size();
     for (int f = 0; ahead && f < n; ++f)
         ahead = cams[f] == lead->ahead_cams[f] && cams[f]->shader && !cams[f]->shader->cb_dirty;
-    TraceFuse tf;
-    int phases = PH_PRE | PH_TRACE;
+    TraceOpts o;
+    TraceFuse& tf = o.fuse;
+    o.prepass = true;
+    o.shard = Shard{shard_rank, shard_count};
     const int state = lead->fuse_state;
     if (ahead && state == rt_device_s::FUSE_FUSED) {
         // the previous k_trace ran this batch's prepass: k_order polls its ray counter, so the frames'
@@ -2350,10 +2492,10 @@ int rt_terrain_trace_ahead(const rt_compute* cams, const rt_compute* scrs, int n
         tf.wait_ctl = lead->fctl;
         tf.wait_total = (uint32_t)lead->fuse_n * (uint32_t)(RT_CAMERA_RES * RT_CAMERA_RES);
         for (rt_device d : lead->fuse_devs) d->ahead_in_pending = false;
-        phases = PH_TRACE;
+        o.prepass = false;
     } else if (ahead && state == rt_device_s::FUSE_NONE) {
         HIP_TRY(hipStreamWaitEvent(lead->stream, lead->ev_ahead, 0)); // the side-stream prepass
-        phases = PH_TRACE;
+        o.prepass = false;
     }
     // (STAGED and never fused, or not covered: the full render, in line; a fused prepass this call does
     // not use is waited for through the frames' ahead_in events, before anything is uploaded)
@@ -2392,17 +2534,17 @@ int rt_terrain_trace_ahead(const rt_compute* cams, const rt_compute* scrs, int n
         const uint32_t tasks = (lead->flags & RT_DEVICE_DEBUG_WITHHOLD_FUSE)
                                    ? 0u : (uint32_t)z->fuse_n * (uint32_t)RT_FUSE_TASKS_PER_FRAME;
         tf.next = FusedPrepass{z->fuse_table.d, z->fctl, tasks};
-        if (!z->ev_fuse_order) HIP_TRY(hipEventCreateWithFlags(&z->ev_fuse_order, hipEventDisableTiming));
+        if (int rc = ensure_event(z->ev_fuse_order)) return rc;
         tf.next_after_order = z->ev_fuse_order;
     }
-    int rc = terrain_render_batch(cams, scrs, n, shard_rank, shard_count, false, phases, 0, -1, nullptr, nullptr, &tf);
+    int rc = batch_trace(fr, o);
     if (z) {
         if (rc) { // not launched: z stays staged (prepasses in line when traced)
             std::lock_guard<std::mutex> lk(g_stream_mu);
             g_fuse_staged[z->ordinal].insert(g_fuse_staged[z->ordinal].begin(), z);
             return rc;
         }
-        if (!z->ev_fuser_done) HIP_TRY(hipEventCreateWithFlags(&z->ev_fuser_done, hipEventDisableTiming));
+        if (int rc = ensure_event(z->ev_fuser_done)) return rc;
         HIP_TRY(hipEventRecord(z->ev_fuser_done, lead->stream));
         z->fuse_state = rt_device_s::FUSE_FUSED;
         for (rt_device d : z->fuse_devs) { // a render of z's frames that does not use the fused prepass waits for it
@@ -2428,14 +2570,14 @@ static int shard_copy(const rt_device* devs, const int* shards, int count, void*
     if (n == 0) return RT_OK;
     rt_device d0 = devs[0];
     if (d0 && host_flag_check(d0)) return RT_ERR_STATE;
-    for (int i = 0; i < n; ++i) {
+    for (int i = 0; i < n; ++i) { // (not devices_enter: a job is checked before its device is flushed, one by one)
         if (!devs[i] || !bufs[i] || shards[i] < 0 || shards[i] >= count) return fail(RT_ERR_INVALID, "bad arguments");
         if (int rc = defer_flush(devs[i])) return rc; // the pending frame is what the shard copy reads or overwrites
         if (devs[i]->width != d0->width || devs[i]->height != d0->height)
             return fail(RT_ERR_INVALID, "shard batch: devices differ in size");
     }
     auto order = [&](rt_device from, rt_device to) -> int {
-        if (!from->sync_ev) HIP_TRY(hipEventCreateWithFlags(&from->sync_ev, hipEventDisableTiming));
+        if (int rc = ensure_event(from->sync_ev)) return rc;
         HIP_TRY(hipEventRecord(from->sync_ev, from->stream));
         HIP_TRY(hipStreamWaitEvent(to->stream, from->sync_ev, 0));
         return RT_OK;
@@ -2457,7 +2599,7 @@ static int shard_copy(const rt_device* devs, const int* shards, int count, void*
     bool others = false;
     for (int i = 1; i < n; ++i) others |= devs[i]->stream != d0->stream;
     if (others) {
-        if (!d0->sync_ev) HIP_TRY(hipEventCreateWithFlags(&d0->sync_ev, hipEventDisableTiming));
+        if (int rc = ensure_event(d0->sync_ev)) return rc;
         HIP_TRY(hipEventRecord(d0->sync_ev, d0->stream));
         for (int i = 1; i < n; ++i)
             if (devs[i]->stream != d0->stream) HIP_TRY(hipStreamWaitEvent(devs[i]->stream, d0->sync_ev, 0));

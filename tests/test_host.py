@@ -213,3 +213,21 @@ def test_deferred_device_binding():
     assert L.rt_device_defer_batch(None, 2) < 0 and b"null" in L.rt_last_error()
     p = C.c_void_p()
     assert L.rt_debug_defer_slot(None, 0, C.byref(p), C.byref(p), C.byref(p)) < 0
+
+
+def test_render_route_under_sanitizers(tmp_path):
+    """tests/tools/render_route_check.cpp: rt_render_route.h's route of one rt_terrain_render call (in line, the
+    prepass stream, the deferred queue, fuse or in-line prepass) for every state that decides it.  Its own main,
+    its own process: nothing of it is loaded into this interpreter."""
+    import shutil
+    import subprocess
+    cxx = shutil.which("g++")
+    assert cxx, "g++ is needed to build tests/tools/render_route_check.cpp"
+    exe = str(tmp_path / "render_route_check")
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan", "-I",
+                    os.path.join(ROOT, "gpgpuraytrace_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "tools", "render_route_check.cpp"), "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.startswith("render_route_check ok")
