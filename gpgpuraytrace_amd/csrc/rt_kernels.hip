@@ -187,7 +187,7 @@ __global__ void __launch_bounds__(BS) k_camerarays_group(const RtConsts* __restr
             noise += used + 1u;
             return d;
         };
-        march_step_with<L, false, true, decltype(dens), true>(c, st, dens);
+        march_step_with<L, false, true>(c, st, dens);
     }
     RayResult rr = march_result(st);
     if (rr.density < 0.0f) rr.pd.w = RT_CAMERA_FAR;
@@ -1489,7 +1489,7 @@ __global__ void __launch_bounds__(TraceThreads<L>::value) k_trace(const RtConsts
                         }
                         return d;
                     };
-                    march_step_with<L, true, true, decltype(dens), true>(cl, st, dens);
+                    march_step_with<L, true, true>(cl, st, dens);
                 }
             }
             // the segments' finished shadows return their fin pool slots (one lane per segment holds it)
@@ -1506,7 +1506,7 @@ __global__ void __launch_bounds__(TraceThreads<L>::value) k_trace(const RtConsts
     // lb: the unit's live rays; st: every lane's march (the finished rays' final states stay in
     // their lanes).  The live rays' states move to their segments (ray r of lb to lanes r*LPR ..),
     // march there with the density's octaves spread over the segment (density_nomadplains_seg,
-    // bit-identical to density_nomadplains; pow_nonneg_flat for the step factor, bit-identical to
+    // bit-identical to density_nomadplains; pow_nonneg_wave for the step factor, bit-identical to
     // pow_nonneg) and come back when every segment's ray has left the march.
     auto primary_seg = [&](const Ctx& cf, March<L, true>& st, bool lv, uint64_t lb, float spx, float spy) {
         if constexpr (L == RT_NOMADPLAINS && kPrimarySeg > 0u && (!STATS || kStatsPrimarySeg)) {
@@ -1549,7 +1549,7 @@ __global__ void __launch_bounds__(TraceThreads<L>::value) k_trace(const RtConsts
                         }
                         return d;
                     };
-                    march_step_with<L, true, false, decltype(dens), true>(cf, sg, dens);
+                    march_step_with<L, true, false>(cf, sg, dens);
                 }
             }
             // back to the rays' lanes (the march changes only these fields)
@@ -1721,7 +1721,7 @@ __global__ void __launch_bounds__(TraceThreads<L>::value) k_trace(const RtConsts
                     uint32_t used;
                     return density_nomadplains_seg<LPR, false>(cp, g, q0, j, base, &used);
                 };
-                march_step_with<L, false, true, decltype(dens), true>(cp, st, dens);
+                march_step_with<L, false, true>(cp, st, dens);
             }
             __builtin_amdgcn_s_setprio(0);
             RayResult rr = march_result(st);
@@ -1939,36 +1939,43 @@ __global__ void __launch_bounds__(TraceThreads<L>::value) k_trace(const RtConsts
                 lv = true;
             }
             __builtin_amdgcn_s_setprio(0);
-            for (uint32_t it = 0;; ++it) {
-                lv = lv && march_live<L, true, false>(cf, st, RT_CAMERA_FAR, max_steps);
-                const uint64_t lb = __ballot(lv);
-                if (lb == 0ull) break;
-                RT_DIAG_LIVE_HIST(if (lane == (uint32_t)__builtin_ctzll(__ballot(1))) atomicAdd(&g_live_hist[__popcll(lb)], 1ull);)
-                RT_DIAG_PRIMARY_STEPS(if (lv) {
+            // The march as a loop of the lanes, not of the wave: a lane leaves it when its ray does, the wave
+            // when its last lane has, and inside it the active lanes are the live rays.  The march state
+            // is then the loop's only carried value and each step updates it in place (as `if (lv) step`
+            // in a loop of the wave, every step first copied the state for the lanes that skip it).
+            uint32_t it = 0;
+            while (lv) {
+                lv = march_live<L, true, false>(cf, st, RT_CAMERA_FAR, max_steps);
+                if (!lv) break;
+                [[maybe_unused]] const uint64_t lb = __ballot(1); // the live rays
+                RT_DIAG_LIVE_HIST(if (lane == (uint32_t)__builtin_ctzll(lb)) atomicAdd(&g_live_hist[__popcll(lb)], 1ull);)
+                RT_DIAG_PRIMARY_STEPS({
                     cf.nz.phase = RT_COUNT_PHASE;
                     count_noise(cf.nz);
                     cf.nz.phase = RT_PHASE_PRIMARY;
                 })
+                // few rays left: they go to the segments, below (lv stays set)
                 if constexpr (L == RT_NOMADPLAINS && kPrimarySeg > 0u && (!STATS || kStatsPrimarySeg)) {
-                    if ((uint32_t)__popcll(lb) <= kPrimarySeg) {
-                        primary_seg(cf, st, lv, lb, pxf + k->aa_off[a][0], pyf + k->aa_off[a][1]);
-                        break;
-                    }
+                    if ((uint32_t)__popcll(lb) <= kPrimarySeg) break;
                 }
 #if RT_FBM_EXIT
                 if constexpr (L == RT_NOMADPLAINS) {
-                    if (lv) { // exact unless the march provably continues after this sample (RT_FBM_EXIT)
-                        const float ns = st.step * k->step_factor;
-                        const bool allow = st.dist + ns < RT_CAMERA_FAR && ns > k->min_limit &&
-                                           !(max_steps > 0 && st.iters + 1 >= max_steps);
-                        march_step_with<L, true, false>(cf, st, [&](f3 q) { return density_nomadplains_x(cf, q, allow); });
-                    }
+                    // exact unless the march provably continues after this sample (RT_FBM_EXIT)
+                    const float ns = st.step * k->step_factor;
+                    const bool allow = st.dist + ns < RT_CAMERA_FAR && ns > k->min_limit &&
+                                       !(max_steps > 0 && st.iters + 1 >= max_steps);
+                    march_step_with<L, true, false>(cf, st, [&](f3 q) { return density_nomadplains_x(cf, q, allow); });
                 } else
 #endif
-                if (lv) march_step<L, true, false>(cf, st);
+                march_step<L, true, false>(cf, st);
                 if (it == 96u) __builtin_amdgcn_s_setprio(1);
                 else if (it == 224u) __builtin_amdgcn_s_setprio(2);
                 else if (it == 384u) __builtin_amdgcn_s_setprio(3);
+                ++it;
+            }
+            if constexpr (L == RT_NOMADPLAINS && kPrimarySeg > 0u && (!STATS || kStatsPrimarySeg)) {
+                // the unit's last <= kPrimarySeg live rays finish on a segment of lanes each
+                if (const uint64_t lb = __ballot(lv)) primary_seg(cf, st, lv, lb, pxf + k->aa_off[a][0], pyf + k->aa_off[a][1]);
             }
             __builtin_amdgcn_s_setprio(0);
             const bool hit = valid && st.d > 0.0f;
@@ -2546,7 +2553,7 @@ __global__ void __launch_bounds__(BS) k_rayquery_seg(const RtConsts* __restrict_
             uint32_t used;
             return density_nomadplains_seg<LPR>(c, g, q, j, base, &used);
         };
-        march_step_with<L, false, true, decltype(dens), true>(c, st, dens);
+        march_step_with<L, false, true>(c, st, dens);
     }
     if (j == 0) store_query_result<STEPS>(st, out, steps, i);
 }
@@ -2702,6 +2709,7 @@ __global__ void k_debug_math(int op, const float* __restrict__ a, const float* _
     case 9: v = rtm::max(x, b[i]); break;
     case 10: v = rtm::min(x, b[i]); break;
     case 11: v = rtm::pow_nonneg(x, b[i]); break;
+    case 13: v = rtm::pow_nonneg_wave(x, b[i]); break; // (a wave = 64 consecutive elements)
     default: v = 0.0f; break;
     }
     y[i] = v;
@@ -2718,9 +2726,11 @@ __global__ void __launch_bounds__(256) k_debug_noise(const RtConsts* __restrict_
     if (i >= n) return;
     Ctx c = make_ctx(k, lds);
     f3 p = rtm::mk(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]);
-    // density 2: noise3d_z0(x, y) (z ignored)
+    // density 2: noise3d_z0(x, y) (z ignored); 3: its FAST variant (|x|, |y| < kFastCellRange)
     if (density == 2) {
         out[i] = noise3d_z0(c.nz, p.x, p.y);
+    } else if (density == 3) {
+        out[i] = noise3d_z0<true>(c.nz, p.x, p.y);
     } else {
         out[i] = density ? get_density<L>(c, p) : noise3d(c.nz, p.x, p.y, p.z);
     }

@@ -195,12 +195,15 @@ RT_HD float exp2_fin(float x)
     return __builtin_ldexpf(p, (int)n);
 }
 
-// pow_nonneg without control flow, for latency-bound code where a single wave's
-// dependency chain is the critical path: every lane runs both polynomials and the
-// special cases are selected afterwards, so it is bit-identical to pow_nonneg for
-// x >= 0 finite and finite y > 0 (x == 0 -> log2 -inf -> exp2 0; the clamped
-// exp2 argument only ever replaces results that are then selected away).
-RT_HD float pow_nonneg_flat(float x, float y)
+// pow_nonneg for the march, without exec-mask regions.  An exp2 argument a = y*log2(x) outside
+// [-150, 128) is rare there, so the range is tested once per wave: a wave without such a lane runs the
+// two polynomials straight through (no default values, no clamp); a wave with one clamps the argument
+// first, an identity in its ordinary lanes, and the exp2 polynomial then returns pow_nonneg's values by
+// itself (below).  A zero base is not rare (the march's bases are clamped at 0, and waves mix zero and
+// nonzero ones): its lane runs the polynomials on frexp's mantissa 0, a finite a, and one select at the
+// end gives pow_nonneg's exp2(-inf) = +0.  Same polynomials and operation order as pow_nonneg:
+// bit-identical for x >= 0 finite and finite y > 0.
+RT_HD float pow_nonneg_wave(float x, float y)
 {
 #if !defined(__HIP_DEVICE_COMPILE__)
     return exp2_fin(y * log2_nonneg(x));
@@ -223,11 +226,16 @@ RT_HD float pow_nonneg_flat(float x, float y)
     p = fma(p, f, 0x1.ec7094p-2f);
     p = fma(p, f, -0x1.715470p-1f);
     p = fma(p, f, 0x1.715476p+0f);
-    const float lg = x == 0.0f ? -__builtin_inff() : fma(f, p, (float)e);
-    const float a = y * lg;
-    const float ac = min(max(a, -150.0f), 128.0f);
-    const float n = rint(ac);
-    const float g = ac - n;
+    const float a = y * fma(f, p, (float)e);
+    // (two ballots of one compare each, or-ed as scalars: a ballot of the or-ed lanes goes through a VGPR)
+    const bool special = (__ballot(!(a >= -150.0f)) | __ballot(a >= 128.0f)) != 0ull;
+    float n = rint(a);
+    float g = a - n;
+    if (__builtin_expect(special, false)) {
+        const float ac = __builtin_amdgcn_fmed3f(a, -150.0f, 128.0f); // min(max(a, -150), 128), a is no NaN
+        n = rint(ac);
+        g = ac - n;
+    }
     float q = 0x1.41a6fep-13f;
     q = fma(q, g, 0x1.5f44f0p-10f);
     q = fma(q, g, 0x1.3b2dfep-7f);
@@ -235,9 +243,10 @@ RT_HD float pow_nonneg_flat(float x, float y)
     q = fma(q, g, 0x1.ebfbdap-3f);
     q = fma(q, g, 0x1.62e430p-1f);
     q = fma(q, g, 1.0f);
-    float r = __builtin_ldexpf(q, (int)n);
-    r = a >= 128.0f ? __builtin_inff() : r;
-    return a < -150.0f ? 0.0f : r;
+    // (a clamped argument needs no select: 128 gives ldexp(1, 128) = +inf and -150 gives
+    // ldexp(1, -150) = +0, half the smallest subnormal rounded to even, as pow_nonneg returns)
+    const float r = __builtin_ldexpf(q, (int)n);
+    return x == 0.0f ? 0.0f : r;
 #endif
 }
 

@@ -225,11 +225,29 @@ __device__ __forceinline__ float noise3d_z0(const NoiseView& nz, float px, float
     const v2f xy = v2(px, py) - v2(fx, fy);
     const v2f uxy = fade2(xy);
     const v2f xy1 = xy + v2(-1.0f, -1.0f);
-    const uint32_t w = *reinterpret_cast<const uint32_t*>(nz.img + texel_offset<FAST>(fx, fy)) & 0x7f7f7f7fu;
-    auto g_at = [&](uint32_t sel) {
-        return *reinterpret_cast<const float4*>(nz.img + __builtin_amdgcn_perm(w, nz.so16, sel));
+    uint32_t to;
+    if constexpr (FAST) {
+        // texel_offset<true> with the x term first: packed as (x, y) the two magic-number fmas take
+        // (fx, fy) as the floors left them; as (y, x) they cost two register copies here
+        const uint32_t mx4 = rtm::bits(fma(fx, 4.0f, kMagic)), my9 = rtm::bits(fma(fy, 512.0f, kMagic));
+        to = (mx4 & 0x1fcu) | (my9 & 0xfe00u);
+    } else {
+        to = texel_offset<false>(fx, fy);
+    }
+    const uint32_t w = *reinterpret_cast<const uint32_t*>(nz.img + to) & 0x7f7f7f7fu;
+    // the z-layer gradient's (x, y) of each corner, as eight one-word loads: the compiler packs the
+    // corners' dots two by two (v_pk_mul / v_pk_fma), and a word it loads on its own lands where
+    // its pair needs it.  Left to itself it merges each corner's two words into one two-word load
+    // whose halves belong to different pairs, and re-pairs them with seven register copies.
+    typedef __attribute__((address_space(3))) const volatile float lds_f;
+    struct G2 {
+        float x, z;
     };
-    const float4 a0 = g_at(0x0c020400u), a1 = g_at(0x0c020500u), b0 = g_at(0x0c020600u), b1 = g_at(0x0c020700u);
+    auto g_at = [&](uint32_t sel) {
+        lds_f* g = (lds_f*)(nz.img + __builtin_amdgcn_perm(w, nz.so16, sel));
+        return G2{g[0], g[2]};
+    };
+    const G2 a0 = g_at(0x0c020400u), a1 = g_at(0x0c020500u), b0 = g_at(0x0c020600u), b1 = g_at(0x0c020700u);
     const float x = xy.x, y = xy.y, x1 = xy1.x, y1 = xy1.y;
     const float g00 = fma(a0.z, y, a0.x * x), g10 = fma(b0.z, y, b0.x * x1);
     const float g01 = fma(a1.z, y1, a1.x * x), g11 = fma(b1.z, y1, b1.x * x1);
@@ -399,7 +417,7 @@ __device__ __forceinline__ float density_nomadplains(const Ctx& c, f3 p)
     const float qm = rtm::max(rtm::max(rtm::abs(q0.x), rtm::abs(q0.y)), rtm::abs(q0.z));
     const bool fast = !__ballot(!(qm * c.nz.oct[n_oct].x < kFastCellRange));
     s = fast ? np_fbm<true>(c, q0, n_oct) : np_fbm<false>(c, q0, n_oct);
-    s = rtm::pow_nonneg(rtm::abs(fma(s, 30.0f, 1.0f)) * 35.0f, c.k->np_expo);
+    s = rtm::pow_nonneg_wave(rtm::abs(fma(s, 30.0f, 1.0f)) * 35.0f, c.k->np_expo);
     count_noise(c.nz);
     const float sn = fast ? noise3d_z0<true>(c.nz, p1.x * 0.007138f, p1.z * 0.007138f)
                           : noise3d_z0<false>(c.nz, p1.x * 0.007138f, p1.z * 0.007138f);
@@ -407,7 +425,7 @@ __device__ __forceinline__ float density_nomadplains(const Ctx& c, f3 p)
     s = terraces(s, p1.y, steep);
     // floor lift: pow(0, 1.5) == 0 exactly, so a wave whose bases are all 0 skips the pow
     const float lb = rtm::sat((-p1.y + 10.0f) * 1.6f);
-    s = fma(__ballot(lb != 0.0f) ? rtm::pow_nonneg(lb, 1.5f) : 0.0f, 19.0f, s);
+    s = fma(__ballot(lb != 0.0f) ? rtm::pow_nonneg_wave(lb, 1.5f) : 0.0f, 19.0f, s);
     return d + s;
 }
 
@@ -619,13 +637,13 @@ __device__ __forceinline__ float density_nomadplains_seg(const Ctx& c, const Seg
         on0 = on[0];
     }
     *octaves = (uint32_t)n_oct;
-    s = rtm::pow_nonneg_flat(rtm::abs(fma(s, 30.0f, 1.0f)) * 35.0f, c.k->np_expo);
+    s = rtm::pow_nonneg_wave(rtm::abs(fma(s, 30.0f, 1.0f)) * 35.0f, c.k->np_expo);
     float steep = rtm::sat((on0 - 0.2f) * 6.0f) * 7.5f;
     s = terraces(s, p1.y, steep);
     // floor lift: pow(0, 1.5) == 0 exactly, so a wave whose bases are all 0 (every
     // sample above y = 25, the common case) skips the polynomial
     const float lb = rtm::sat((-p1.y + 10.0f) * 1.6f);
-    const float lift = __ballot(lb != 0.0f) ? rtm::pow_nonneg_flat(lb, 1.5f) : 0.0f;
+    const float lift = __ballot(lb != 0.0f) ? rtm::pow_nonneg_wave(lb, 1.5f) : 0.0f;
     s = fma(lift, 19.0f, s);
     if constexpr (kDpp) return seg_bcast<LPR>(d + s); // the first lane's density to its segment
     return d + s;
@@ -797,7 +815,7 @@ __device__ __forceinline__ bool march_live(const Ctx& c, const March<L, CALCFOG>
     return m.dist < enddist && m.step > c.k->min_limit && !(max_steps > 0 && m.iters >= max_steps);
 }
 
-template <int L, bool CALCFOG, bool SKIPREFINE, class Density, bool FLAT = false>
+template <int L, bool CALCFOG, bool SKIPREFINE, class Density>
 __device__ __forceinline__ void march_step_with(const Ctx& c, March<L, CALCFOG>& m, Density density)
 {
     const RtConsts* k = c.k;
@@ -830,8 +848,7 @@ __device__ __forceinline__ void march_step_with(const Ctx& c, March<L, CALCFOG>&
         float stepmult;
         // pow(0, y > 0) == 0: a wave of zero bases (all samples within 5 of the
         // surface) skips the polynomial
-        if constexpr (FLAT) stepmult = 1.0f + (__ballot(sx != 0.0f) ? rtm::pow_nonneg_flat(sx, k->density_factor) : 0.0f);
-        else stepmult = 1.0f + rtm::pow_nonneg(sx, k->density_factor);
+        stepmult = 1.0f + (__ballot(sx != 0.0f) ? rtm::pow_nonneg_wave(sx, k->density_factor) : 0.0f);
         m.step = m.step * k->step_factor;
         m.lastStep = m.step * stepmult;
         m.dist = m.dist + m.lastStep;

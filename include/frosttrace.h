@@ -449,13 +449,15 @@ int rt_terrain_trace_rays_device(rt_compute cs, const void* rays_device, int n,
 /* ---- diagnostics (primitive-level parity tests; no reference counterpart) ----
  * rt_debug_math: device evaluation of the numeric primitives of DESIGN.md §Numerics
  *   (op 0 exp2, 1 log2, 2 exp, 3 sin, 4 cos, 5 sqrt, 6 rcp, 7 rsqrt, 8 pow, 9 max,
- *   10 min, 11 pow for x >= 0); host arrays of n floats (b may be NULL for unary ops).
+ *   10 min, 11 pow for x >= 0, 13 the march's wave-tested pow for x >= 0: a wave is 64
+ *   consecutive elements); host arrays of n floats (b may be NULL for unary ops).
  *   op 12 sweeps the nomadplains octave-count estimate over the n floats whose bit
  *   patterns follow bits(a[0]) and writes 3 uint32 to out: unflagged estimates that differ
  *   from the exact count, flagged estimates, patterns swept.
  * rt_debug_noise: noise3d (density = 0, noise.hlsl:153-179) or the compute's landscape
  *   getDensity (density = 1) at n points (xyz interleaved), with the compute's
- *   current tables and constants. */
+ *   current tables and constants; density = 2: nomadplains' steep noise noise3d(x, y, 0)
+ *   (z ignored), 3: its short-integer-path variant (|x|, |y| < 8192). */
 int rt_debug_math(rt_device dev, int op, const float* a, const float* b, float* out, int n);
 int rt_debug_noise(rt_compute cs, const float* xyz, float* out, int n, int density);
 /* rt_debug_sky (ABI 4): the sky of n view directions (xyz interleaved) with the compute's current
