@@ -46,6 +46,15 @@ class RtRayOptions(C.Structure):
     _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("eye", C.c_float * 3), ("max_blocks", C.c_uint32)]
 
 
+RT_SURFACE_PARAMS = 8  # rt_surface_options.flags beside RT_RAYS_*: t_min, t_max, stepmod, max_steps are read
+RT_SURFACE_RAY_RANGE = 16  # the packed rays' spare words are t_min_i, t_max_i
+
+
+class RtSurfaceOptions(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("eye", C.c_float * 3), ("max_blocks", C.c_uint32),
+                ("t_min", C.c_float), ("t_max", C.c_float), ("stepmod", C.c_float), ("max_steps", C.c_uint32)]
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -123,6 +132,8 @@ SIGNATURES = {
     "rt_shard_unpack_batch": (_i, [C.POINTER(_vp), C.POINTER(_i), _i, C.POINTER(_vp), _i]),
     "rt_terrain_trace_rays": (_i, [_vp, _vp, _vp, _i, C.POINTER(RtRayOptions), _vp, _vp]),
     "rt_terrain_trace_rays_device": (_i, [_vp, _vp, _i, C.POINTER(RtRayOptions), _vp, _vp]),
+    "rt_terrain_trace_surface": (_i, [_vp, _vp, _vp, _vp, _i, C.POINTER(RtSurfaceOptions), _vp, _vp]),
+    "rt_terrain_trace_surface_device": (_i, [_vp, _vp, _i, C.POINTER(RtSurfaceOptions), _vp, _vp]),
     "rt_noise_generate": (_i, [C.c_uint32, _i, _vp, _vp]),
     "rt_terrain_set_target_depths": (_i, [_vp, _vp]),
     "rt_recorder_create": (_i, [_vp, _i, _i, _cp, C.POINTER(_vp)]),

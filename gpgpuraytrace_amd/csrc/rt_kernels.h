@@ -144,6 +144,26 @@ struct RtRayQuery {
 };
 bool rt_launch_rayquery(const RtLaunch& a, const RtRayQuery& q);
 
+// A surface query (rt_terrain_trace_surface): the refined march tracescreen runs for its pixels
+// (traceRay with skiprefine off, tracing.hlsl:47-105) and getNormal (:107-116) for the same packed rays ->
+// results[2n] (pd.xyz, pd.w | normal, density; the normal 0 where density <= 0) and, if set, steps[n].  t_min,
+// t_max, stepmod and max_steps (0: unbounded) hold for every ray; with ray_range the rays' spare words are
+// t_min_i and t_max_i instead.  Shapes, grid and counter as RtRayQuery's.
+struct RtSurfQuery {
+    const float4* rays;
+    float4* results;
+    uint32_t* steps; // may be null
+    uint32_t n;
+    float eye[3];
+    int bs, lpr;
+    uint32_t blocks;
+    uint32_t* counter;
+    float t_min, t_max, stepmod;
+    int max_steps;
+    bool ray_range;
+};
+bool rt_launch_surfquery(const RtLaunch& a, const RtSurfQuery& q);
+
 #define RT_TILE 32
 #define RT_FIN_SLOTS 1536 // k_trace's fin pool slots per block
 #define RT_AO_POOL_SLOTS 256 // k_trace's AO counter slots per block (LDS) and their colours (cpool)

@@ -2670,6 +2670,220 @@ bool rt_launch_rayquery(const RtLaunch& a, const RtRayQuery& q)
 }
 
 // ---------------------------------------------------------------------------
+// Surface queries (rt_terrain_trace_surface): the march tracescreen runs for its pixels (traceRay with
+// skiprefine off, tracescreen.hlsl:20) and getNormal (tracing.hlsl:107-116) for rays read from memory, in the
+// two shapes of the ray queries above.  Ray i is the same two 16-byte loads; with RANGE their spare words are
+// t_min_i and t_max_i.  Its result is two 16-byte stores: pd.xyz, pd.w | normal, density (the normal 0 where
+// density <= 0: no hit).
+namespace {
+
+#ifdef RT_SURFQ_UTIL
+// diagnostic build (scripts/surface_query_bench.py) of k_surfquery's waves: march steps, live lanes summed
+// over them, normal evaluations (a wave's ended lanes together), lanes summed over those
+__device__ unsigned long long g_surfq_util[4];
+#endif
+
+struct SurfArgs {
+    float ex, ey, ez;
+    float t_min, t_max, stepmod;
+    int max_steps;
+};
+
+template <bool STEPS, class M, class Normal>
+__device__ __forceinline__ void store_surface_result(const M& st, float4* __restrict__ out,
+                                                     uint32_t* __restrict__ steps, uint32_t i, Normal normal)
+{
+    const RayResult rr = march_result(st);
+    f3 nrm = rtm::mk(0.0f, 0.0f, 0.0f);
+    if (rr.density > 0.0f) nrm = normal(f4{rr.pd.x, rr.pd.y, rr.pd.z, rr.density});
+    gstore(out + 2 * (size_t)i, make_float4(rr.pd.x, rr.pd.y, rr.pd.z, rr.pd.w));
+    gstore(out + 2 * (size_t)i + 1, make_float4(nrm.x, nrm.y, nrm.z, rr.density));
+    if constexpr (STEPS) steps[i] = (uint32_t)st.iters;
+}
+
+// Segments (nomadplains, few rays: a pick is one ray, and on one lane its longest march takes milliseconds):
+// k_rayquery_seg's shape.  The march state is replicated over the segment, so the hit test is segment-uniform
+// and the whole segment takes the normal's three taps through density_nomadplains_seg.
+template <bool STEPS, bool RANGE, int BS, int LPR>
+__global__ void __launch_bounds__(BS) k_surfquery_seg(const RtConsts* __restrict__ k,
+                                                       const uint32_t* __restrict__ perm2d,
+                                                       const float4* __restrict__ grad,
+                                                       const float4* __restrict__ rays, float4* __restrict__ out,
+                                                       uint32_t* __restrict__ steps, uint32_t n, SurfArgs a)
+{
+    constexpr int L = RT_NOMADPLAINS;
+    __shared__ __attribute__((aligned(16))) uint32_t lds[kNoiseLdsWords];
+    load_noise_lds(lds, perm2d, grad, k);
+    const uint32_t i = blockIdx.x * (uint32_t)(BS / LPR) + threadIdx.x / (uint32_t)LPR;
+    if (i >= n) return; // whole segments leave together
+    Ctx c = make_ctx(k, lds);
+    c.eye = rtm::mk(a.ex, a.ey, a.ez);
+    const uint32_t j = threadIdx.x & (LPR - 1u), base = threadIdx.x & 63u & ~(LPR - 1u);
+    const SegOctaves<LPR> g = seg_octaves<LPR>(c, j);
+    const float4 o = rays[2 * (size_t)i], d = rays[2 * (size_t)i + 1];
+    const float t0 = RANGE ? o.w : a.t_min, endd = RANGE ? d.w : a.t_max;
+    auto dens = [&](f3 q) {
+        uint32_t used;
+        return density_nomadplains_seg<LPR>(c, g, q, j, base, &used);
+    };
+    March<L, false> st;
+    march_begin(c, st, rtm::mk(o.x, o.y, o.z), t0, a.stepmod, rtm::mk(d.x, d.y, d.z));
+    while (march_live<L, false, false>(c, st, endd, a.max_steps)) march_step_with<L, false, false>(c, st, dens);
+    const RayResult rr = march_result(st);
+    f3 nrm = rtm::mk(0.0f, 0.0f, 0.0f);
+    if (rr.density > 0.0f) nrm = get_normal_with(c, f4{rr.pd.x, rr.pd.y, rr.pd.z, rr.density}, dens);
+    if (j == 0) {
+        gstore(out + 2 * (size_t)i, make_float4(rr.pd.x, rr.pd.y, rr.pd.z, rr.pd.w));
+        gstore(out + 2 * (size_t)i + 1, make_float4(nrm.x, nrm.y, nrm.z, rr.density));
+        if constexpr (STEPS) steps[i] = (uint32_t)st.iters;
+    }
+}
+
+// Lanes (every landscape, many rays): k_rayquery's persistent grid and refill.  The ended lanes of a wave
+// evaluate their normals together where their results are stored: at the refill and at the end.
+template <int L, bool STEPS, bool RANGE>
+__global__ void __launch_bounds__(1024) k_surfquery(const RtConsts* __restrict__ k, const uint32_t* __restrict__ perm2d,
+                                                    const float4* __restrict__ grad, const float4* __restrict__ rays,
+                                                    float4* __restrict__ out, uint32_t* __restrict__ steps, uint32_t n,
+                                                    SurfArgs a, uint32_t* __restrict__ counter, uint32_t refill_live)
+{
+#ifdef RT_SURFQ_UTIL
+    uint32_t util_wave = 0, util_lane = 0, util_nwave = 0, util_nlane = 0;
+#endif
+    __shared__ __attribute__((aligned(16))) uint32_t lds[kNoiseLdsWords];
+    load_noise_lds(lds, perm2d, grad, k);
+    Ctx c = make_ctx(k, lds);
+    c.eye = rtm::mk(a.ex, a.ey, a.ez);
+    const uint32_t lane = threadIdx.x & 63u;
+    auto normal = [&](f4 pd) { return get_normal<L>(c, pd); };
+    March<L, false> st{};
+    float endd = a.t_max; // per lane with RANGE
+    uint32_t idx = 0;
+    bool has = false, live = false; // has: idx is a ray of the query whose result is not stored yet
+    bool more = true;               // (uniform) the counter has not passed n
+    for (;;) {
+        uint64_t lv = __ballot(live);
+        if (more && (uint32_t)__popcll(lv) <= refill_live) {
+            const uint32_t cnt = 64u - (uint32_t)__popcll(lv); // >= 1: refill_live <= 63
+            const uint32_t first = wave_fetch(counter, lane, cnt);
+#ifdef RT_SURFQ_UTIL
+            if (const uint64_t nm = __ballot(!live && has && st.d > 0.0f)) {
+                ++util_nwave;
+                util_nlane += (uint32_t)__popcll(nm);
+            }
+#endif
+            if (!live) {
+                if (has) store_surface_result<STEPS>(st, out, steps, idx, normal);
+                idx = first + lane_rank(~lv);
+                has = idx < n;
+                if (has) {
+                    const float4 o = rays[2 * (size_t)idx], d = rays[2 * (size_t)idx + 1];
+                    if constexpr (RANGE) endd = d.w;
+                    march_begin(c, st, rtm::mk(o.x, o.y, o.z), RANGE ? o.w : a.t_min, a.stepmod, rtm::mk(d.x, d.y, d.z));
+                    live = march_live<L, false, false>(c, st, endd, a.max_steps);
+                }
+            }
+            more = first + cnt < n;
+            lv = __ballot(live);
+        }
+        if (!lv) {
+            if (!more) break;
+            continue; // every new ray ended before its first step: claim again
+        }
+#ifdef RT_SURFQ_UTIL
+        ++util_wave;
+        util_lane += (uint32_t)__popcll(lv);
+#endif
+        if (live) {
+            march_step<L, false, false>(c, st);
+            live = march_live<L, false, false>(c, st, endd, a.max_steps);
+        }
+    }
+#ifdef RT_SURFQ_UTIL
+    if (const uint64_t nm = __ballot(has && st.d > 0.0f)) {
+        ++util_nwave;
+        util_nlane += (uint32_t)__popcll(nm);
+    }
+#endif
+    if (has) store_surface_result<STEPS>(st, out, steps, idx, normal);
+#ifdef RT_SURFQ_UTIL
+    if (lane == 0) {
+        atomicAdd(&g_surfq_util[0], (unsigned long long)util_wave);
+        atomicAdd(&g_surfq_util[1], (unsigned long long)util_lane);
+        atomicAdd(&g_surfq_util[2], (unsigned long long)util_nwave);
+        atomicAdd(&g_surfq_util[3], (unsigned long long)util_nlane);
+    }
+#endif
+}
+
+SurfArgs surf_args(const RtSurfQuery& q)
+{
+    return SurfArgs{q.eye[0], q.eye[1], q.eye[2], q.t_min, q.t_max, q.stepmod, q.max_steps};
+}
+
+template <int L, bool STEPS, bool RANGE>
+void launch_surfquery_lanes_as(const RtLaunch& a, const RtSurfQuery& q)
+{
+    constexpr uint32_t thr = RT_RAYQ_REFILL < 63 ? RT_RAYQ_REFILL : 63; // as launch_rayquery_lanes
+    hipLaunchKernelGGL((k_surfquery<L, STEPS, RANGE>), dim3(q.blocks), dim3(1024), 0, a.stream, a.consts, a.perm2d,
+                       a.grad, q.rays, q.results, q.steps, q.n, surf_args(q), q.counter, thr);
+}
+
+template <int L>
+void launch_surfquery_lanes(const RtLaunch& a, const RtSurfQuery& q)
+{
+    if (q.steps) {
+        if (q.ray_range) launch_surfquery_lanes_as<L, true, true>(a, q);
+        else launch_surfquery_lanes_as<L, true, false>(a, q);
+    } else {
+        if (q.ray_range) launch_surfquery_lanes_as<L, false, true>(a, q);
+        else launch_surfquery_lanes_as<L, false, false>(a, q);
+    }
+}
+
+template <bool STEPS, bool RANGE, int BS, int LPR>
+void launch_surfquery_seg_as(const RtLaunch& a, const RtSurfQuery& q)
+{
+    hipLaunchKernelGGL((k_surfquery_seg<STEPS, RANGE, BS, LPR>), dim3(q.blocks), dim3(BS), 0, a.stream, a.consts,
+                       a.perm2d, a.grad, q.rays, q.results, q.steps, q.n, surf_args(q));
+}
+
+template <int BS, int LPR>
+void launch_surfquery_seg(const RtLaunch& a, const RtSurfQuery& q)
+{
+    if (q.steps) {
+        if (q.ray_range) launch_surfquery_seg_as<true, true, BS, LPR>(a, q);
+        else launch_surfquery_seg_as<true, false, BS, LPR>(a, q);
+    } else {
+        if (q.ray_range) launch_surfquery_seg_as<false, true, BS, LPR>(a, q);
+        else launch_surfquery_seg_as<false, false, BS, LPR>(a, q);
+    }
+}
+
+} // namespace
+
+bool rt_launch_surfquery(const RtLaunch& a, const RtSurfQuery& q)
+{
+    if (q.n == 0 || q.blocks == 0) return true;
+    if (q.lpr > 1) { // segments: the pairs of rt_launch_rayquery
+        if (a.landscape != RT_NOMADPLAINS) return false;
+        if (q.bs == RT_PREPASS_BS1 && q.lpr == RT_PREPASS_LPR1) launch_surfquery_seg<RT_PREPASS_BS1, RT_PREPASS_LPR1>(a, q);
+        else if (q.bs == 512 && q.lpr == 32) launch_surfquery_seg<512, 32>(a, q);
+        else if (q.bs == 512 && q.lpr == 8) launch_surfquery_seg<512, 8>(a, q);
+        else if (q.bs == 512 && q.lpr == 4) launch_surfquery_seg<512, 4>(a, q);
+        else return false;
+        return true;
+    }
+    switch (a.landscape) {
+    case RT_TESTING: launch_surfquery_lanes<RT_TESTING>(a, q); break;
+    case RT_SIMPLE: launch_surfquery_lanes<RT_SIMPLE>(a, q); break;
+    case RT_GREENROCKS: launch_surfquery_lanes<RT_GREENROCKS>(a, q); break;
+    default: launch_surfquery_lanes<RT_NOMADPLAINS>(a, q); break;
+    }
+    return true;
+}
+
+// ---------------------------------------------------------------------------
 // Diagnostics: device evaluation of the numeric primitives, noise3d and
 // getDensity for the primitive-level parity tests (tests/test_gpu_parity.py).
 namespace {
@@ -2827,6 +3041,21 @@ extern "C" int rt_debug_rayquery_util(unsigned long long* out, int reset)
         if (hipMemcpyToSymbol(HIP_SYMBOL(g_rayq_util), zero, 16) != hipSuccess) return -1;
     }
     return 2;
+}
+#endif
+
+#ifdef RT_SURFQ_UTIL
+// diagnostic build: copies (and with reset != 0 clears) k_surfquery's (wave steps, live lanes summed over them,
+// normal evaluations, lanes summed over those)
+extern "C" int rt_debug_surfquery_util(unsigned long long* out, int reset)
+{
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_surfq_util), 32) != hipSuccess) return -1;
+    if (reset) {
+        static const unsigned long long zero[4] = {};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(g_surfq_util), zero, 32) != hipSuccess) return -1;
+    }
+    return 4;
 }
 #endif
 

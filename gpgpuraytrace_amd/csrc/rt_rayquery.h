@@ -117,6 +117,91 @@ inline int plan(int n, bool nomadplains, uint32_t flags, uint32_t max_blocks, in
     return OK;
 }
 
+// ---- surface queries (rt_terrain_trace_surface): their own option block, the same shapes ----
+
+// rt_surface_options.flags beside kEye / kForceSegments / kForceLanes (RT_SURFACE_*)
+constexpr uint32_t kSurfParams = 8u, kSurfRayRange = 16u;
+// the first version of rt_surface_options: size, flags, eye[3], max_blocks, t_min, t_max, stepmod, max_steps
+constexpr uint32_t kSurfOptSizeV1 = 40u;
+// the values a tracescreen pixel gets with an empty CellDistance (tracescreen.hlsl:20, tracing.hlsl:3-4)
+constexpr float kSurfTMin = 0.01f, kSurfTMax = 5000.0f, kSurfStepmod = 1.0f;
+// Auto mode on nomadplains for surface queries: segments up to this many rays, lanes beyond.  The refined march
+// is about 1.3x the prepass's iterations, so the segment shape's static deal grows sooner than the ray queries'
+// (kAutoSegmentsMax).  Measured (profiles/r10/surface_query.md): segments 0.82 ms against lanes 2.82 ms at 32,768
+// rays, 1.61 against 2.89 at 65,536, 3.24 against 2.96 at 131,072, 4.82 against 3.00 at 196,608, 6.41 against
+// 3.11 at 262,144.  Segments are linear in n from 65,536 on (24.7 us per 1,024 rays), which puts the crossing
+// near 119,000 rays; the rule sits just below it.
+constexpr int kSurfAutoSegmentsMax = 112 * 1024;
+
+struct SurfOptions {
+    uint32_t flags = 0;
+    float eye[3] = {0.0f, 0.0f, 0.0f};
+    uint32_t max_blocks = 0;
+    float t_min = kSurfTMin, t_max = kSurfTMax, stepmod = kSurfStepmod;
+    uint32_t max_steps = 0; // 0: unbounded
+};
+
+inline bool finite_f(float x) { return x - x == 0.0f; }
+
+// `opt` is the caller's rt_surface_options (may be null: the defaults), read through its size field only as far
+// as the first version reaches; a larger size is a later version whose extra fields this build ignores.  The
+// four trailing fields count with RT_SURFACE_PARAMS only.
+inline int parse_surface_options(const void* opt, SurfOptions* out, const char** why)
+{
+    *out = SurfOptions{};
+    if (!opt) return OK;
+    uint32_t size;
+    std::memcpy(&size, opt, 4);
+    if (size < kSurfOptSizeV1) {
+        *why = "rt_surface_options.size is smaller than the struct's first version";
+        return INVALID;
+    }
+    const char* p = static_cast<const char*>(opt);
+    std::memcpy(&out->flags, p + 4, 4);
+    std::memcpy(out->eye, p + 8, 12);
+    std::memcpy(&out->max_blocks, p + 20, 4);
+    if ((out->flags & kForceSegments) && (out->flags & kForceLanes)) {
+        *why = "RT_RAYS_FORCE_SEGMENTS and RT_RAYS_FORCE_LANES are both set";
+        return INVALID;
+    }
+    if (out->flags & kSurfParams) {
+        std::memcpy(&out->t_min, p + 24, 4);
+        std::memcpy(&out->t_max, p + 28, 4);
+        std::memcpy(&out->stepmod, p + 32, 4);
+        std::memcpy(&out->max_steps, p + 36, 4);
+        if (!finite_f(out->stepmod) || !(out->stepmod > 0.0f)) {
+            *why = "rt_surface_options.stepmod must be finite and above 0";
+            return INVALID;
+        }
+        if (!(out->t_max >= out->t_min)) { // (a NaN bound too)
+            *why = "rt_surface_options.t_max is below t_min";
+            return INVALID;
+        }
+    }
+    return OK;
+}
+
+// the kernels count a ray's iterations in an int: a cap beyond it is no cap that a march could reach
+inline int surface_max_steps(uint32_t max_steps) { return max_steps > 0x7fffffffu ? 0x7fffffff : (int)max_steps; }
+
+// the plan of a surface query: plan() with the surface queries' own auto rule
+inline int plan_surface(int n, bool nomadplains, uint32_t flags, uint32_t max_blocks, int cus, int prepass_bs1,
+                        int prepass_lpr1, Plan* out, const char** why)
+{
+    uint32_t f = flags & (kForceSegments | kForceLanes);
+    if (!f && nomadplains) f = n <= kSurfAutoSegmentsMax ? kForceSegments : kForceLanes;
+    return plan(n, nomadplains, f, max_blocks, cus, prepass_bs1, prepass_lpr1, out, why);
+}
+
+// ray i of a packed query with its range: ox oy oz t_min_i dx dy dz t_max_i (ranges: 2n floats)
+inline void pack_ranges(const float* ranges, int n, float* packed)
+{
+    for (int i = 0; i < n; ++i) {
+        packed[(size_t)i * 8 + 3] = ranges[2 * (size_t)i];
+        packed[(size_t)i * 8 + 7] = ranges[2 * (size_t)i + 1];
+    }
+}
+
 // ray i of a packed query: ox oy oz _ dx dy dz _
 inline void pack(const float* origins, const float* dirs, int n, float* packed)
 {

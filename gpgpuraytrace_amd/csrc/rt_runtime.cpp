@@ -2884,6 +2884,114 @@ extern "C" int rt_terrain_trace_rays(rt_compute c, const float* origins, const f
 }
 
 // ---------------------------------------------------------------------------
+// rt_terrain_trace_surface: caller-supplied rays marched as tracescreen marches its pixels' (refined), with the
+// normal at each hit (include/frosttrace.h).  The query state (Shader::query, the claim counter) is the ray queries'.
+namespace {
+
+int trace_surface_enqueue(rt_compute c, const void* rays_device, int n, const rtq::SurfOptions& o, void* results_device,
+                          void* steps_device)
+{
+    rt_device dev = c->dev;
+    Shader* s = c->shader;
+    float eye[3];
+    if (int rc = sync_query_consts(dev, s, eye)) return rc;
+    if (o.flags & rtq::kEye) memcpy(eye, o.eye, sizeof(eye));
+    rtq::Plan p;
+    const char* why = "";
+    if (int rc = rtq::plan_surface(n, s->landscape == RT_NOMADPLAINS, o.flags, o.max_blocks, dev->num_cus - dev->reserve_cus,
+                                   RT_PREPASS_BS1, RT_PREPASS_LPR1, &p, &why))
+        return fail(rc, "rt_terrain_trace_surface: %s", why);
+    RtLaunch a = make_launch(dev, s);
+    a.consts = s->query.d_consts;
+    a.grad = s->query.d_grad;
+    RtSurfQuery q{};
+    q.rays = (const float4*)rays_device;
+    q.results = (float4*)results_device;
+    q.steps = (uint32_t*)steps_device;
+    q.n = (uint32_t)n;
+    memcpy(q.eye, eye, sizeof(eye));
+    q.bs = p.bs;
+    q.lpr = p.lpr;
+    q.blocks = p.blocks;
+    q.t_min = o.t_min;
+    q.t_max = o.t_max;
+    q.stepmod = o.stepmod;
+    q.max_steps = rtq::surface_max_steps(o.max_steps);
+    q.ray_range = (o.flags & rtq::kSurfRayRange) != 0;
+    if (p.shape == rtq::LANES) {
+        if (!dev->rq_counter) HIP_TRY(hipMalloc(&dev->rq_counter, 64));
+        HIP_TRY(hipMemsetAsync(dev->rq_counter, 0, 4, dev->stream));
+        q.counter = dev->rq_counter;
+    }
+    if (!rt_launch_surfquery(a, q)) return fail(RT_ERR_UNSUPPORTED, "rt_terrain_trace_surface: no kernel for this shape");
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+// the checks both forms share, in the order the header gives; *o: the parsed options
+int trace_surface_check(rt_compute c, int n, const rt_surface_options* opt, rtq::SurfOptions* o)
+{
+    if (!c) return fail(RT_ERR_INVALID, "null compute");
+    const char* why = "";
+    if (int rc = rtq::check_count(n, &why)) return fail(rc, "rt_terrain_trace_surface: %s", why);
+    if (int rc = rtq::parse_surface_options(opt, o, &why)) return fail(rc, "rt_terrain_trace_surface: %s", why);
+    if (!c->shader) return fail(RT_ERR_STATE, "no current shader");
+    if ((o->flags & rtq::kForceSegments) && c->shader->landscape != RT_NOMADPLAINS)
+        return fail(RT_ERR_UNSUPPORTED, "rt_terrain_trace_surface: the segment shape exists for nomadplains only");
+    return RT_OK;
+}
+
+} // namespace
+
+extern "C" int rt_terrain_trace_surface_device(rt_compute c, const void* rays_device, int n, const rt_surface_options* opt,
+                                               void* results_device, void* steps_device)
+{
+    rtq::SurfOptions o;
+    if (int rc = trace_surface_check(c, n, opt, &o)) return rc;
+    if (n > 0 && (!rays_device || !results_device)) return fail(RT_ERR_INVALID, "rt_terrain_trace_surface_device: null rays or results");
+    if (int rc = check_texture(c->shader)) return rc;
+    if (int rc = host_flag_check(c->dev)) return rc;
+    if (n == 0) return RT_OK;
+    HIP_TRY(hipSetDevice(c->dev->ordinal));
+    return trace_surface_enqueue(c, rays_device, n, o, results_device, steps_device);
+}
+
+extern "C" int rt_terrain_trace_surface(rt_compute c, const float* origins, const float* dirs, const float* ranges, int n,
+                                        const rt_surface_options* opt, float* results, uint32_t* steps)
+{
+    rtq::SurfOptions o;
+    if (int rc = trace_surface_check(c, n, opt, &o)) return rc;
+    if (n > 0 && (!origins || !dirs || !results)) return fail(RT_ERR_INVALID, "rt_terrain_trace_surface: null origins, dirs or results");
+    if (int rc = check_texture(c->shader)) return rc;
+    if (int rc = host_flag_check(c->dev)) return rc;
+    if (n == 0) return RT_OK;
+    // the host form packs the rays itself, so the spare words are the ranges exactly when it was given some
+    if (ranges) o.flags |= rtq::kSurfRayRange;
+    else o.flags &= ~rtq::kSurfRayRange;
+    rt_device dev = c->dev;
+    HIP_TRY(hipSetDevice(dev->ordinal));
+    // one device block: the packed rays, the results, the step counts
+    const size_t nr = (size_t)n, rays_b = nr * 32, res_b = nr * 32, steps_b = steps ? nr * 4 : 0;
+    std::vector<float> packed(nr * 8);
+    rtq::pack(origins, dirs, n, packed.data());
+    if (ranges) rtq::pack_ranges(ranges, n, packed.data());
+    char* d = nullptr;
+    HIP_TRY(hipMalloc(&d, rays_b + res_b + steps_b));
+    auto run = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(d, packed.data(), rays_b, hipMemcpyHostToDevice, dev->stream));
+        if (int rc = trace_surface_enqueue(c, d, n, o, d + rays_b, steps ? d + rays_b + res_b : nullptr)) return rc;
+        HIP_TRY(hipMemcpyAsync(results, d + rays_b, res_b, hipMemcpyDeviceToHost, dev->stream));
+        if (steps) HIP_TRY(hipMemcpyAsync(steps, d + rays_b + res_b, steps_b, hipMemcpyDeviceToHost, dev->stream));
+        HIP_TRY(hipStreamSynchronize(dev->stream));
+        return RT_OK;
+    };
+    const int rc = run();
+    if (rc) (void)hipStreamSynchronize(dev->stream); // whatever was queued is over before the block is freed
+    (void)hipFree(d);
+    return rc;
+}
+
+// ---------------------------------------------------------------------------
 // rt_readback_*: the asynchronous readback ring (struct rt_readback_s above; include/frosttrace.h)
 int rt_readback_create(rt_device d, int format, int depth, rt_readback* out)
 {

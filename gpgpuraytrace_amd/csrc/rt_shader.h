@@ -911,6 +911,20 @@ __device__ __forceinline__ f3 get_normal(const Ctx& c, f4 pd)
     return rtm::normalize(rtm::mk(dx, dy, dz));
 }
 
+// get_normal with its three taps through `density` (a segment's density_nomadplains_seg, whose lanes take the
+// taps together): the same operations in the same order, so the same bits as get_normal
+template <class Density>
+__device__ __forceinline__ f3 get_normal_with(const Ctx& c, f4 pd, Density density)
+{
+    const f3 p = rtm::mk(pd.x, pd.y, pd.z);
+    const float dist = rtm::length(rtm::sub(p, c.eye));
+    const float nd = dist * 0.005f;
+    const float dx = density(rtm::mk(p.x - nd, p.y - 0.0f, p.z - 0.0f)) - pd.w;
+    const float dy = density(rtm::mk(p.x - 0.0f, p.y - nd, p.z - 0.0f)) - pd.w;
+    const float dz = density(rtm::mk(p.x - 0.0f, p.y - 0.0f, p.z - nd)) - pd.w;
+    return rtm::normalize(rtm::mk(dx, dy, dz));
+}
+
 // tracing.hlsl:124-134 (x scaled by Projection._22, y by _11, as written)
 __device__ __forceinline__ void get_pixel_ray(const Ctx& c, float px, float py, f3* outp, f3* outdir)
 {

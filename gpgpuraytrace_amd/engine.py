@@ -666,8 +666,50 @@ class Terrain:
                                                 results_ptr or None, steps_ptr or None)
         return rc == _native.RT_OK
 
+    def trace_surface(self, origins, dirs, ranges=None, eye=None, t_min=None, t_max=None, stepmod=None, max_steps=0,
+                      steps=False, mode="auto", max_blocks=0):
+        """rt_terrain_trace_surface: where n rays of the caller's own meet the surface and its normal there --
+        the refined march tracescreen runs for its pixels (tracing.hlsl:47-105, skiprefine off) and getNormal
+        (:107-116).  origins, dirs: (n, 3), dirs used as given; ranges: (n, 2) t_min_i, t_max_i per ray, or None
+        for t_min / t_max (defaults 0.01 and 5000); stepmod default 1; max_steps 0 is unbounded, and a ray whose
+        step count equals a cap may be mid-refinement.  eye: the LOD eye and getNormal's (default: the camera's).
+        Returns results (n, 8) float32 -- last sample xyz, distance | unit normal, density; a hit is
+        results[:, 7] > 0 and a miss has a zero normal -- or (results, steps); None if the call fails
+        (lib().rt_last_error()).  mode, max_blocks: as trace_rays.  Blocking; needs set_camera() first."""
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise ValueError("trace_surface: %d origins, %d dirs" % (len(o), len(d)))
+        n = len(o)
+        rg = None
+        if ranges is not None:
+            rg = np.ascontiguousarray(ranges, np.float32).reshape(-1, 2)
+            if len(rg) != n:
+                raise ValueError("trace_surface: %d rays, %d ranges" % (n, len(rg)))
+        opt = surface_options(eye, mode, max_blocks, t_min, t_max, stepmod, max_steps)
+        self.update_shaders()
+        res = np.empty((n, 8), np.float32)
+        st = np.empty(n, np.uint32) if steps else None
+        rc = lib().rt_terrain_trace_surface(self.camera_compute._h, o.ctypes.data, d.ctypes.data,
+                                            rg.ctypes.data if rg is not None else None, n, C.byref(opt),
+                                            res.ctypes.data, st.ctypes.data if steps else None)
+        if rc != _native.RT_OK:
+            return None
+        return (res, st) if steps else res
 
-RAY_MODES = {"auto": 0, "segments": _native.RT_RAYS_FORCE_SEGMENTS, "lanes": _native.RT_RAYS_FORCE_LANES}
+    def trace_surface_device(self, rays_ptr, n, results_ptr, steps_ptr=0, ray_range=False, eye=None, t_min=None,
+                             t_max=None, stepmod=None, max_steps=0, mode="auto", max_blocks=0):
+        """rt_terrain_trace_surface_device: the same for device arrays -- rays_ptr n x 8 float32 (pack_rays'
+        layout; with ray_range its spare words are the rays' ranges), results_ptr n x 8 float32, steps_ptr n
+        uint32 or 0 -- enqueued on the device's stream with no host synchronisation.  True on success."""
+        opt = surface_options(eye, mode, max_blocks, t_min, t_max, stepmod, max_steps, ray_range)
+        self.update_shaders()
+        rc = lib().rt_terrain_trace_surface_device(self.camera_compute._h, rays_ptr or None, int(n), C.byref(opt),
+                                                   results_ptr or None, steps_ptr or None)
+        return rc == _native.RT_OK
+
+
+RAY_MODES ={"auto": 0, "segments": _native.RT_RAYS_FORCE_SEGMENTS, "lanes": _native.RT_RAYS_FORCE_LANES}
 
 
 def ray_options(eye=None, mode="auto", max_blocks=0):
@@ -684,8 +726,33 @@ def ray_options(eye=None, mode="auto", max_blocks=0):
     return opt
 
 
-def pack_rays(origins, dirs):
-    """The device form's ray layout: (n, 8) float32 rows ox oy oz 0 dx dy dz 0 (two 16-byte loads per ray)."""
+def surface_options(eye=None, mode="auto", max_blocks=0, t_min=None, t_max=None, stepmod=None, max_steps=0,
+                    ray_range=False):
+    """An rt_surface_options block: ray_options' fields, and with any of t_min, t_max, stepmod, max_steps given
+    RT_SURFACE_PARAMS with the others at their defaults (0.01, 5000, 1, unbounded)."""
+    if mode not in RAY_MODES:
+        raise ValueError("ray query mode %r: one of %s" % (mode, sorted(RAY_MODES)))
+    opt = _native.RtSurfaceOptions()
+    opt.size = C.sizeof(_native.RtSurfaceOptions)
+    opt.flags = RAY_MODES[mode]
+    if eye is not None:
+        opt.flags |= _native.RT_RAYS_EYE
+        opt.eye[:] = [float(x) for x in np.asarray(eye, np.float32).reshape(3)]
+    opt.max_blocks = int(max_blocks)
+    if t_min is not None or t_max is not None or stepmod is not None or max_steps:
+        opt.flags |= _native.RT_SURFACE_PARAMS
+        opt.t_min = 0.01 if t_min is None else float(t_min)
+        opt.t_max = 5000.0 if t_max is None else float(t_max)
+        opt.stepmod = 1.0 if stepmod is None else float(stepmod)
+        opt.max_steps = int(max_steps)
+    if ray_range:
+        opt.flags |= _native.RT_SURFACE_RAY_RANGE
+    return opt
+
+
+def pack_rays(origins, dirs, ranges=None):
+    """The device form's ray layout: (n, 8) float32 rows ox oy oz 0 dx dy dz 0 (two 16-byte loads per ray); with
+    ranges (n, 2) the spare words are the ray's t_min and t_max (surface queries' RT_SURFACE_RAY_RANGE)."""
     o = np.asarray(origins, np.float32).reshape(-1, 3)
     d = np.asarray(dirs, np.float32).reshape(-1, 3)
     if o.shape != d.shape:
@@ -693,6 +760,12 @@ def pack_rays(origins, dirs):
     out = np.zeros((len(o), 8), np.float32)
     out[:, 0:3] = o
     out[:, 4:7] = d
+    if ranges is not None:
+        r = np.asarray(ranges, np.float32).reshape(-1, 2)
+        if len(r) != len(o):
+            raise ValueError("pack_rays: %d rays, %d ranges" % (len(o), len(r)))
+        out[:, 3] = r[:, 0]
+        out[:, 7] = r[:, 1]
     return out
 
 

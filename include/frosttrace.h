@@ -446,6 +446,62 @@ int rt_terrain_trace_rays(rt_compute cs, const float* origins, const float* dirs
 int rt_terrain_trace_rays_device(rt_compute cs, const void* rays_device, int n,
                                  const rt_ray_options* opt, void* results_device, void* steps_device);
 
+/* ---- surface queries (ABI 9, additive; no reference counterpart) ----
+ * Where a ray of the host's own meets the SURFACE, and the surface's normal there: picking and placement.
+ * rt_terrain_trace_rays above returns the prepass's answer -- the first sample that landed inside the terrain,
+ * up to metres below the surface, and no normal.  A surface query runs the refined march tracescreen runs for
+ * its pixels and getNormal.  For ray i with origin_i and dir_i and one LOD eye E per call:
+ *     rr       = traceRay(origin_i, t_min, t_max, stepmod, dir_i, calcfog off, skiprefine OFF)  (tracing.hlsl:47-105)
+ *     hit      = rr.density > 0                                                          (tracescreen.hlsl:29)
+ *     n        = hit ? getNormal(float4(rr.pd.xyz, rr.density)) : (0, 0, 0)               (tracing.hlsl:107-116)
+ *     result_i = { float4(rr.pd.xyz, rr.pd.w), float4(n, rr.density) },  steps_i = the loop's iteration count
+ * so result_i is 8 floats: position, distance | unit normal, density; a hit is result_i[7] > 0.
+ *   dir   is used as given, as for rt_terrain_trace_rays: its LENGTH enters the first step (tracing.hlsl:54).
+ *   E     replaces Eye in getDensity (nomadplains' octave count) AND in getNormal's eps = 0.005 |p - Eye|.
+ *         Without RT_RAYS_EYE it is the compute's current Eye variable.  One per call.
+ *   Defaults: t_min 0.01, t_max 5000, stepmod 1, max_steps 0 (unbounded) -- what a tracescreen pixel gets with an
+ *         empty CellDistance.  With RT_SURFACE_PARAMS the option block's t_min, t_max, stepmod and max_steps
+ *         hold instead (they are not read without the flag).  RECORDING and the landscape constants come from
+ *         the compute.
+ *   Refinement always ends on an inside sample: after a hit the step shrinks x0.3 and the loop condition is
+ *         tested next, after a miss the step grows.  rr.pd.xyz is the last sample and rr.pd.w the loop's dist
+ *         after the back-off, exactly as the reference returns them.
+ *   max_steps > 0: a ray with steps_i == max_steps was ended by the cap and may be mid-refinement (its last
+ *         sample need not be inside, nor near the surface).
+ *   A zero dir gives, with the default range, 0 steps and { (0, 0, 0, t_min), (0, 0, 0, 0) }.  Non-finite
+ *         inputs, or a zero dir with a large t_min, give unspecified results; the march still ends.
+ *   Per-ray range: with RT_SURFACE_RAY_RANGE the packed ray's two spare words are t_min_i and t_max_i
+ *         (ox oy oz t_min_i dx dy dz t_max_i) and replace t_min / t_max: segment queries such as line of
+ *         sight between two points, or a start plane per ray as CellDistance gives tracescreen.  Without the
+ *         flag the words are ignored.  The host form sets it itself when ranges != NULL (2n floats).
+ * rt_surface_options (opt may be NULL: all defaults): size = sizeof(rt_surface_options) of the caller's header
+ *   (later versions append fields); flags: RT_RAYS_EYE, RT_RAYS_FORCE_SEGMENTS, RT_RAYS_FORCE_LANES as above
+ *   (identical bits in either shape), RT_SURFACE_PARAMS, RT_SURFACE_RAY_RANGE; max_blocks as above.
+ * rt_terrain_trace_surface: host arrays, xyz interleaved (origins, dirs: 3n floats; ranges: 2n floats or NULL;
+ *   results: 8n floats; steps: n uint32 or NULL); blocking.
+ * rt_terrain_trace_surface_device: device arrays (rays n x 8 floats, 16-byte aligned; results n x 8 floats,
+ *   16-byte aligned; steps n uint32 or NULL), enqueued on the compute's device stream with no host
+ *   synchronisation: order other streams with rt_device_wait_event / rt_device_record_event.
+ * Both: n == 0 is RT_OK and launches nothing.  RT_ERR_INVALID: n < 0, n > 2^26, a NULL compute or required
+ *   array, opt->size below the first version (40), both force flags, and with RT_SURFACE_PARAMS a stepmod that
+ *   is <= 0 or not finite or t_max < t_min.  RT_ERR_UNSUPPORTED: forced segments off nomadplains.  RT_ERR_STATE
+ *   without texPerm2D bound, or with the fail-safe word set.  A query reads no frame state and changes none: it
+ *   flushes no deferred frame, invalidates no ahead / fused prepass or captured graph, and uploads the
+ *   constants it needs to a copy of its own, so it may run between any two renders. */
+enum { RT_SURFACE_PARAMS = 8, RT_SURFACE_RAY_RANGE = 16 };
+typedef struct {
+    uint32_t size;
+    uint32_t flags;
+    float eye[3];
+    uint32_t max_blocks;
+    float t_min, t_max, stepmod;
+    uint32_t max_steps;
+} rt_surface_options;
+int rt_terrain_trace_surface(rt_compute cs, const float* origins, const float* dirs, const float* ranges, int n,
+                             const rt_surface_options* opt, float* results, uint32_t* steps);
+int rt_terrain_trace_surface_device(rt_compute cs, const void* rays_device, int n,
+                                    const rt_surface_options* opt, void* results_device, void* steps_device);
+
 /* ---- diagnostics (primitive-level parity tests; no reference counterpart) ----
  * rt_debug_math: device evaluation of the numeric primitives of DESIGN.md §Numerics
  *   (op 0 exp2, 1 log2, 2 exp, 3 sin, 4 cos, 5 sqrt, 6 rcp, 7 rsqrt, 8 pow, 9 max,

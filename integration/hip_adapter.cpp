@@ -88,6 +88,18 @@ bool ComputeHIP::traceRays(const float* origins, const float* dirs, int n, float
     return rt_terrain_trace_rays(cs, origins, dirs, n, &opt, results, nullptr) == RT_OK;
 }
 
+bool ComputeHIP::traceSurface(const float* origins, const float* dirs, int n, float* results, const float* eye,
+                              const float* ranges)
+{
+    rt_surface_options opt = {};
+    opt.size = (uint32_t)sizeof(opt);
+    if (eye) {
+        opt.flags = RT_RAYS_EYE;
+        for (int i = 0; i < 3; ++i) opt.eye[i] = eye[i];
+    }
+    return rt_terrain_trace_surface(cs, origins, dirs, ranges, n, &opt, results, nullptr) == RT_OK;
+}
+
 DeviceHIP::DeviceHIP(IWindow* window) : IDevice(kDeviceApiHip, window) { }
 DeviceHIP::~DeviceHIP()
 {

@@ -82,6 +82,13 @@ public:
     // position, the hit distance or 5000 for a miss); eye: the level-of-detail eye (3 floats), nullptr = the
     // compute's Eye variable.  Blocking.  The reference's only hit query is the last prepass (Flyby.cpp:44-90).
     bool traceRays(const float* origins, const float* dirs, int n, float* results, const float* eye = nullptr);
+    // (adapter extension) rt_terrain_trace_surface (ABI 9, additive): where those rays meet the SURFACE and its
+    // normal there -- the refined march of tracescreen's pixels (tracing.hlsl:47-105, skiprefine off) and getNormal
+    // (:107-116): picking and placement.  results: 8n floats (the last sample's position, its distance | the unit
+    // normal, the density: a hit is density > 0, a miss has a zero normal); ranges: 2n floats t_min_i, t_max_i,
+    // nullptr = 0.01 to 5000; eye: the LOD eye and getNormal's, nullptr = the compute's Eye variable.  Blocking.
+    bool traceSurface(const float* origins, const float* dirs, int n, float* results, const float* eye = nullptr,
+                      const float* ranges = nullptr);
     rt_compute handle() const { return cs; }
 
 private:
