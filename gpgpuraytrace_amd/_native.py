@@ -134,6 +134,9 @@ SIGNATURES = {
     "rt_terrain_trace_rays_device": (_i, [_vp, _vp, _i, C.POINTER(RtRayOptions), _vp, _vp]),
     "rt_terrain_trace_surface": (_i, [_vp, _vp, _vp, _vp, _i, C.POINTER(RtSurfaceOptions), _vp, _vp]),
     "rt_terrain_trace_surface_device": (_i, [_vp, _vp, _i, C.POINTER(RtSurfaceOptions), _vp, _vp]),
+    # shaded queries (one sample a ray, no AO): the tracescreen compute; results (8n floats), rgba8 (n), steps (2n)
+    "rt_terrain_shade_rays": (_i, [_vp, _vp, _vp, _vp, _i, C.POINTER(RtSurfaceOptions), _vp, _vp, _vp]),
+    "rt_terrain_shade_rays_device": (_i, [_vp, _vp, _i, C.POINTER(RtSurfaceOptions), _vp, _vp, _vp]),
     "rt_noise_generate": (_i, [C.c_uint32, _i, _vp, _vp]),
     "rt_terrain_set_target_depths": (_i, [_vp, _vp]),
     "rt_recorder_create": (_i, [_vp, _i, _i, _cp, C.POINTER(_vp)]),

@@ -164,6 +164,25 @@ struct RtSurfQuery {
 };
 bool rt_launch_surfquery(const RtLaunch& a, const RtSurfQuery& q);
 
+// A shaded query (rt_terrain_shade_rays): the sample tracescreen.hlsl:16-48 computes (one sample, no AO) for the
+// same packed rays -> results[2n] (colour, pd.w | pd.xyz, density), rgba8[n] and steps[2n] (primary, shadow
+// iterations), each if set; results or rgba8 must be.  The constants (a.consts) carry the query's eye, for the
+// sky.  Parameters as RtSurfQuery's; the lanes shape only (bs 1024), so the counter is required.
+struct RtShadeQuery {
+    const float4* rays;
+    float4* results; // may be null
+    uint32_t* rgba8; // may be null
+    uint32_t* steps; // may be null
+    uint32_t n;
+    float eye[3];
+    uint32_t blocks;
+    uint32_t* counter;
+    float t_min, t_max, stepmod;
+    int max_steps;
+    bool ray_range;
+};
+bool rt_launch_shadequery(const RtLaunch& a, const RtShadeQuery& q);
+
 #define RT_TILE 32
 #define RT_FIN_SLOTS 1536 // k_trace's fin pool slots per block
 #define RT_AO_POOL_SLOTS 256 // k_trace's AO counter slots per block (LDS) and their colours (cpool)

@@ -2884,6 +2884,200 @@ bool rt_launch_surfquery(const RtLaunch& a, const RtSurfQuery& q)
 }
 
 // ---------------------------------------------------------------------------
+// Shaded queries (rt_terrain_shade_rays): the sample tracescreen.hlsl:16-48 computes for a pixel ray -- the refined
+// primary march with fog, then for a hit getNormal, getColor with its shadow march, the fog and sky blends, for a
+// miss the sky -- for rays read from memory.  One sample per ray, no AO.  Ray i is the surface queries' two 16-byte
+// loads; its result is two 16-byte stores (colour, pd.w | pd.xyz, density), a packed RGBA8 word and two step
+// counts (primary, shadow), each where its pointer is set.
+namespace {
+
+#ifdef RT_SHADEQ_UTIL
+// diagnostic build (scripts/shade_query_bench.py) of k_shadequery's waves: march steps, live lanes summed over
+// them, shading visits (a wave's ended primaries together), lanes summed over those
+__device__ unsigned long long g_shadeq_util[4];
+#endif
+
+template <bool STEPS>
+__device__ __forceinline__ void store_shade_result(float4* __restrict__ out, uint32_t* __restrict__ out8,
+                                                   uint32_t* __restrict__ steps, uint32_t i, f3 col, float dist,
+                                                   int shadow_iters)
+{
+    if (out) gstore(out + 2 * (size_t)i, make_float4(col.x, col.y, col.z, dist));
+    if (out8) out8[i] = unorm8(col.x) | (unorm8(col.y) << 8) | (unorm8(col.z) << 16) | 0xff000000u;
+    if constexpr (STEPS) steps[2 * (size_t)i + 1] = (uint32_t)shadow_iters;
+}
+
+// Lanes (every landscape): k_surfquery's persistent grid and refill, a lane's ray in one of two marches: PRIMARY
+// (refining, to the ray's range and the cap) then, for a hit, SHADOW (skiprefine, to 100, no cap).  Both kinds
+// step in the one march_step_with of the loop, skiprefine per lane.  Everything else runs where a wave visits
+// the refill point, for all its lanes that ended a march since the last visit:
+//   an ended PRIMARY: the sky's scattering; a hit then takes getNormal and getColor up to its shadow ray and goes
+//     live again as that ray (SHADOW), a miss takes the space colour, blends and stores;
+//   an ended SHADOW: the rest of getColor, the fog and sky blends, the store;
+//   a lane without a ray claims one from the query's counter.
+// A SHADOW lane carries beside its March the hit's ShadePre, distance, fog and rayleigh term; the hit's position
+// is the shadow march's origin and the density is stored when the primary ends.
+// The loop ends when the counter has passed n, no lane is live and no lane holds a ray: a visit is due whenever
+// the live lanes are few enough and there is something to do (rays to claim, or a lane with an ended march), a
+// visit claims at least one ray or moves every ended march on by one phase (of two a ray), and a wave with no
+// live lane always visits or leaves.
+template <int L, bool STEPS, bool RANGE>
+__global__ void __launch_bounds__(1024) k_shadequery(const RtConsts* __restrict__ k, const uint32_t* __restrict__ perm2d,
+                                                     const float4* __restrict__ grad, const float4* __restrict__ rays,
+                                                     float4* __restrict__ out, uint32_t* __restrict__ out8,
+                                                     uint32_t* __restrict__ steps, uint32_t n, SurfArgs a,
+                                                     uint32_t* __restrict__ counter, uint32_t refill_live)
+{
+#ifdef RT_SHADEQ_UTIL
+    uint32_t util_wave = 0, util_lane = 0, util_swave = 0, util_slane = 0;
+#endif
+    __shared__ __attribute__((aligned(16))) uint32_t lds[kNoiseLdsWords];
+    load_noise_lds(lds, perm2d, grad, k);
+    Ctx c = make_ctx(k, lds);
+    c.eye = rtm::mk(a.ex, a.ey, a.ez);
+    const uint32_t lane = threadIdx.x & 63u;
+    auto dens = [&](f3 q) { return get_density<L>(c, q); };
+    March<L, true> st{};
+    ShadePre sp{};                       // SHADOW: getColor's terms before its shadow ray
+    f4 pfog = {0.0f, 0.0f, 0.0f, 0.0f}; // SHADOW: the primary's fcolord
+    f3 ray = rtm::mk(0.0f, 0.0f, 0.0f); // SHADOW: scat.rayleigh
+    float pdist = 0.0f;                  // SHADOW: the primary's pd.w
+    float endd = a.t_max;                // the live march's end: the ray's range, 100 for a shadow ray
+    uint32_t idx = 0;
+    bool has = false, live = false; // has: idx is a ray of the query whose result is not stored yet
+    bool shadow = false;            // the lane's march is its ray's shadow march
+    bool more = true;               // (uniform) the counter has not passed n
+    for (;;) {
+        uint64_t lv = __ballot(live);
+        if ((uint32_t)__popcll(lv) <= refill_live && (more || __ballot(has && !live))) {
+            const bool ended = has && !live;
+#ifdef RT_SHADEQ_UTIL
+            if (const uint64_t sm = __ballot(ended && !shadow)) {
+                ++util_swave;
+                util_slane += (uint32_t)__popcll(sm);
+            }
+#endif
+            if (ended && !shadow) { // tracescreen.hlsl:20-38 after the primary march
+                const RayResult rr = march_result(st);
+                // normalize(dir_i): march_begin's dir * rcp(length(dir)) is rtm::normalize's own product
+                const f3 pdn = st.dir;
+                if (out) gstore(out + 2 * (size_t)idx + 1, make_float4(rr.pd.x, rr.pd.y, rr.pd.z, rr.density));
+                if constexpr (STEPS) steps[2 * (size_t)idx] = (uint32_t)st.iters;
+                const SkyColor scat = get_rayleigh_mie(c, pdn);
+                if (rr.density > 0.0f) {
+                    const f3 hp = rtm::mk(rr.pd.x, rr.pd.y, rr.pd.z);
+                    const f3 nrm = get_normal<L>(c, f4{hp.x, hp.y, hp.z, rr.density});
+                    sp = shade_pre<L>(c, hp, nrm, pdn, rr.pd.w);
+                    pdist = rr.pd.w;
+                    if constexpr (March<L, true>::FOG) pfog = rr.fc;
+                    ray = scat.rayleigh;
+                    // color.hlsl:51 traceRay(p, 0.4, 100, precision, SunDirection, fog, skiprefine)
+                    march_begin(c, st, hp, 0.4f, sp.precision, c.sun);
+                    endd = 100.0f;
+                    shadow = true;
+                    live = march_live_skip(c, st, endd, 0, true);
+                } else {
+                    const float space = get_space_color(c, pdn);
+                    const f3 sky = rtm::mk((scat.mie.x + scat.rayleigh.x) + space, (scat.mie.y + scat.rayleigh.y) + space,
+                                           (scat.mie.z + scat.rayleigh.z) + space);
+                    float sa = rr.pd.w * 0.0005f;
+                    sa = rtm::sat(sa * sa);
+                    f3 col = rtm::mk(rtm::lerp(sky.x, rr.fc.x, rr.fc.w), rtm::lerp(sky.y, rr.fc.y, rr.fc.w),
+                                     rtm::lerp(sky.z, rr.fc.z, rr.fc.w));
+                    col = rtm::mk(rtm::lerp(col.x, sky.x, sa), rtm::lerp(col.y, sky.y, sa), rtm::lerp(col.z, sky.z, sa));
+                    store_shade_result<STEPS>(out, out8, steps, idx, col, rr.pd.w, 0);
+                    has = false;
+                }
+            }
+            if (has && !live && shadow) { // color.hlsl:53-71 after the shadow ray, tracescreen.hlsl:33-35
+                f3 col = shade_post(c, sp, st.d, st.f.w);
+                float sa = pdist * 0.0005f;
+                sa = rtm::sat(sa * sa);
+                col = rtm::mk(rtm::lerp(col.x, pfog.x, pfog.w), rtm::lerp(col.y, pfog.y, pfog.w),
+                              rtm::lerp(col.z, pfog.z, pfog.w));
+                col = rtm::mk(rtm::lerp(col.x, ray.x, sa), rtm::lerp(col.y, ray.y, sa), rtm::lerp(col.z, ray.z, sa));
+                store_shade_result<STEPS>(out, out8, steps, idx, col, pdist, st.iters);
+                has = false;
+                shadow = false;
+            }
+            if (more) {
+                const uint64_t idle = __ballot(!has);
+                const uint32_t cnt = (uint32_t)__popcll(idle);
+                const uint32_t first = wave_fetch(counter, lane, cnt);
+                if (!has) {
+                    idx = first + lane_rank(idle);
+                    has = idx < n;
+                    if (has) {
+                        const float4 o = rays[2 * (size_t)idx], d = rays[2 * (size_t)idx + 1];
+                        endd = RANGE ? d.w : a.t_max;
+                        march_begin(c, st, rtm::mk(o.x, o.y, o.z), RANGE ? o.w : a.t_min, a.stepmod, rtm::mk(d.x, d.y, d.z));
+                        live = march_live_skip(c, st, endd, a.max_steps, false);
+                    }
+                }
+                more = first + cnt < n;
+            }
+            lv = __ballot(live);
+        }
+        if (!lv) {
+            if (!more && !__ballot(has)) break;
+            continue; // lanes hold marches that ended before their first step, or there are rays to claim: visit again
+        }
+#ifdef RT_SHADEQ_UTIL
+        ++util_wave;
+        util_lane += (uint32_t)__popcll(lv);
+#endif
+        if (live) {
+            march_step_with<L, true, false>(c, st, dens, shadow);
+            live = march_live_skip(c, st, endd, shadow ? 0 : a.max_steps, shadow);
+        }
+    }
+#ifdef RT_SHADEQ_UTIL
+    if (lane == 0) {
+        atomicAdd(&g_shadeq_util[0], (unsigned long long)util_wave);
+        atomicAdd(&g_shadeq_util[1], (unsigned long long)util_lane);
+        atomicAdd(&g_shadeq_util[2], (unsigned long long)util_swave);
+        atomicAdd(&g_shadeq_util[3], (unsigned long long)util_slane);
+    }
+#endif
+}
+
+template <int L, bool STEPS, bool RANGE>
+void launch_shadequery_as(const RtLaunch& a, const RtShadeQuery& q)
+{
+    constexpr uint32_t thr = RT_SHADEQ_REFILL < 63 ? RT_SHADEQ_REFILL : 63;
+    const SurfArgs sa{q.eye[0], q.eye[1], q.eye[2], q.t_min, q.t_max, q.stepmod, q.max_steps};
+    hipLaunchKernelGGL((k_shadequery<L, STEPS, RANGE>), dim3(q.blocks), dim3(1024), 0, a.stream, a.consts, a.perm2d,
+                       a.grad, q.rays, q.results, q.rgba8, q.steps, q.n, sa, q.counter, thr);
+}
+
+template <int L>
+void launch_shadequery(const RtLaunch& a, const RtShadeQuery& q)
+{
+    if (q.steps) {
+        if (q.ray_range) launch_shadequery_as<L, true, true>(a, q);
+        else launch_shadequery_as<L, true, false>(a, q);
+    } else {
+        if (q.ray_range) launch_shadequery_as<L, false, true>(a, q);
+        else launch_shadequery_as<L, false, false>(a, q);
+    }
+}
+
+} // namespace
+
+bool rt_launch_shadequery(const RtLaunch& a, const RtShadeQuery& q)
+{
+    if (q.n == 0 || q.blocks == 0) return true;
+    if (!q.counter || (!q.results && !q.rgba8)) return false;
+    switch (a.landscape) {
+    case RT_TESTING: launch_shadequery<RT_TESTING>(a, q); break;
+    case RT_SIMPLE: launch_shadequery<RT_SIMPLE>(a, q); break;
+    case RT_GREENROCKS: launch_shadequery<RT_GREENROCKS>(a, q); break;
+    default: launch_shadequery<RT_NOMADPLAINS>(a, q); break;
+    }
+    return true;
+}
+
+// ---------------------------------------------------------------------------
 // Diagnostics: device evaluation of the numeric primitives, noise3d and
 // getDensity for the primitive-level parity tests (tests/test_gpu_parity.py).
 namespace {
@@ -3054,6 +3248,21 @@ extern "C" int rt_debug_surfquery_util(unsigned long long* out, int reset)
     if (reset) {
         static const unsigned long long zero[4] = {};
         if (hipMemcpyToSymbol(HIP_SYMBOL(g_surfq_util), zero, 32) != hipSuccess) return -1;
+    }
+    return 4;
+}
+#endif
+
+#ifdef RT_SHADEQ_UTIL
+// diagnostic build: copies (and with reset != 0 clears) k_shadequery's (wave steps, live lanes summed over them,
+// shading visits, lanes summed over those)
+extern "C" int rt_debug_shadequery_util(unsigned long long* out, int reset)
+{
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_shadeq_util), 32) != hipSuccess) return -1;
+    if (reset) {
+        static const unsigned long long zero[4] = {};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(g_shadeq_util), zero, 32) != hipSuccess) return -1;
     }
     return 4;
 }

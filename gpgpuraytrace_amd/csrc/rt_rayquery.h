@@ -1,6 +1,7 @@
-// rt_rayquery.h -- host-only decisions of rt_terrain_trace_rays (include/frosttrace.h): the option
-// block's validation and the choice of the kernel shape, its lanes per ray and its grid.  No HIP in
-// here: tests/tools/rayquery_check.cpp drives it stand-alone under ASan + UBSan.
+// rt_rayquery.h -- host-only decisions of rt_terrain_trace_rays, rt_terrain_trace_surface and
+// rt_terrain_shade_rays (include/frosttrace.h): the option blocks' validation and the choice of the kernel
+// shape, its lanes per ray and its grid.  No HIP in here: tests/tools/rayquery_check.cpp, surfquery_check.cpp
+// and shadequery_check.cpp drive it stand-alone under ASan + UBSan.
 #pragma once
 
 #include <cstddef>
@@ -191,6 +192,19 @@ inline int plan_surface(int n, bool nomadplains, uint32_t flags, uint32_t max_bl
     uint32_t f = flags & (kForceSegments | kForceLanes);
     if (!f && nomadplains) f = n <= kSurfAutoSegmentsMax ? kForceSegments : kForceLanes;
     return plan(n, nomadplains, f, max_blocks, cus, prepass_bs1, prepass_lpr1, out, why);
+}
+
+// ---- shaded queries (rt_terrain_shade_rays): the surface queries' option block, the lanes shape only ----
+
+// the plan of a shaded query: always lanes (there is no segment shape), its grid min(ceil(n / 1024), cus,
+// max_blocks); cus: the CUs a persistent grid may take
+inline int plan_shade(int n, uint32_t flags, uint32_t max_blocks, int cus, Plan* out, const char** why)
+{
+    if (flags & kForceSegments) {
+        *why = "shaded queries have no segment shape";
+        return UNSUPPORTED;
+    }
+    return plan(n, false, kForceLanes, max_blocks, cus, 0, 0, out, why);
 }
 
 // ray i of a packed query with its range: ox oy oz t_min_i dx dy dz t_max_i (ranges: 2n floats)

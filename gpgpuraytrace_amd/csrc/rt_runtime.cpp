@@ -497,6 +497,24 @@ float rd_f(const std::vector<uint8_t>& b, int off)
     return f;
 }
 
+// The sky constants that follow from k.eye (getRayleighMieColor's prologue, sky.hlsl:88-100); k.sky_sos is set.
+// build_consts' last step, and a shaded query's after it put its own eye in place.
+void consts_sky_eye(RtConsts& k)
+{
+    const float outerRadius = (float)(200.0 * (double)1.025f);
+    float camHeight = rtm::fma(k.eye[1], 0.001f, 200.0f);
+    camHeight = rtm::max(camHeight, 0.0f);
+    k.sky_dist_to_top = outerRadius - camHeight;
+    k.sky_start[0] = k.eye[0] * 0.001f;
+    k.sky_start[1] = camHeight;
+    k.sky_start[2] = k.eye[2] * 0.001f;
+    rtm::f3 sn = rtm::normalize(rtm::mk(k.sky_start[0], k.sky_start[1], k.sky_start[2]));
+    k.sky_start_n[0] = sn.x;
+    k.sky_start_n[1] = sn.y;
+    k.sky_start_n[2] = sn.z;
+    k.sky_depth0 = rtm::exp(k.sky_sos * (200.0f - camHeight));
+}
+
 // Build the constant block from the cbuffer shadows (tracing.hlsl:6-41,
 // sky.hlsl:1-16/:74-80, landscape color constants, antialiasing.hlsl:9-49).
 void build_consts(const Shader& s, const rt_device_s& dev, RtConsts& k)
@@ -575,18 +593,7 @@ void build_consts(const Shader& s, const rt_device_s& dev, RtConsts& k)
     k.sky_rcp_samples = (float)(1.0 / 3.0);
     k.sky_fscale = fScale;
     k.sky_sos = sos;
-    // eye-dependent (getRayleighMieColor prologue, sky.hlsl:88-100)
-    float camHeight = rtm::fma(k.eye[1], 0.001f, 200.0f);
-    camHeight = rtm::max(camHeight, 0.0f);
-    k.sky_dist_to_top = outerRadius - camHeight;
-    k.sky_start[0] = k.eye[0] * 0.001f;
-    k.sky_start[1] = camHeight;
-    k.sky_start[2] = k.eye[2] * 0.001f;
-    rtm::f3 sn = rtm::normalize(rtm::mk(k.sky_start[0], k.sky_start[1], k.sky_start[2]));
-    k.sky_start_n[0] = sn.x;
-    k.sky_start_n[1] = sn.y;
-    k.sky_start_n[2] = sn.z;
-    k.sky_depth0 = rtm::exp(sos * (200.0f - camHeight));
+    consts_sky_eye(k);
 
     static const float off1[1][2] = {{0, 0}};
     static const float off2[2][2] = {{4, 4}, {-4, -4}};
@@ -2763,8 +2770,9 @@ extern "C" int rt_debug_sky(rt_compute c, const float* dirs, float* out, int n)
 // rt_terrain_trace_rays: caller-supplied rays marched as the prepass marches its own (include/frosttrace.h)
 namespace {
 
-// the compute's constants and gradients as they are NOW, in the query's own device copies (Shader::query)
-int sync_query_consts(rt_device dev, Shader* s, float default_eye[3])
+// the compute's constants and gradients as they are NOW, in the query's own device copies (Shader::query).
+// sky_eye (shaded queries): the eye the copy's Eye and sky constants are for, instead of the compute's.
+int sync_query_consts(rt_device dev, Shader* s, float default_eye[3], const float* sky_eye = nullptr)
 {
     Shader::QueryConsts& q = s->query;
     if (!q.d_consts) HIP_TRY(hipMalloc(&q.d_consts, sizeof(RtConsts)));
@@ -2778,6 +2786,10 @@ int sync_query_consts(rt_device dev, Shader* s, float default_eye[3])
         memcpy(grad.data(), nz.data(), std::min(grad.size(), nz.size()));
     }
     for (int i = 0; i < 3; ++i) default_eye[i] = hk.eye[i];
+    if (sky_eye) {
+        for (int i = 0; i < 3; ++i) hk.eye[i] = sky_eye[i];
+        consts_sky_eye(hk);
+    }
     if (q.valid && !memcmp(&hk, &q.last, sizeof(RtConsts)) && grad == q.grad_last) return RT_OK;
     q.valid = false;
     if (int rc = q.consts_staging.upload(dev->stream, q.d_consts, &hk, sizeof(RtConsts))) return rc;
@@ -2982,6 +2994,119 @@ extern "C" int rt_terrain_trace_surface(rt_compute c, const float* origins, cons
         if (int rc = trace_surface_enqueue(c, d, n, o, d + rays_b, steps ? d + rays_b + res_b : nullptr)) return rc;
         HIP_TRY(hipMemcpyAsync(results, d + rays_b, res_b, hipMemcpyDeviceToHost, dev->stream));
         if (steps) HIP_TRY(hipMemcpyAsync(steps, d + rays_b + res_b, steps_b, hipMemcpyDeviceToHost, dev->stream));
+        HIP_TRY(hipStreamSynchronize(dev->stream));
+        return RT_OK;
+    };
+    const int rc = run();
+    if (rc) (void)hipStreamSynchronize(dev->stream); // whatever was queued is over before the block is freed
+    (void)hipFree(d);
+    return rc;
+}
+
+// ---------------------------------------------------------------------------
+// rt_terrain_shade_rays: caller-supplied rays shaded as tracescreen shades its pixels' (include/frosttrace.h).  The
+// query state (Shader::query, the claim counter) is the ray queries'; the constants' copy carries the query's eye.
+namespace {
+
+int shade_rays_enqueue(rt_compute c, const void* rays_device, int n, const rtq::SurfOptions& o, void* results_device,
+                       void* rgba8_device, void* steps_device)
+{
+    rt_device dev = c->dev;
+    Shader* s = c->shader;
+    float eye[3];
+    if (int rc = sync_query_consts(dev, s, eye, (o.flags & rtq::kEye) ? o.eye : nullptr)) return rc;
+    if (o.flags & rtq::kEye) memcpy(eye, o.eye, sizeof(eye));
+    rtq::Plan p;
+    const char* why = "";
+    if (int rc = rtq::plan_shade(n, o.flags, o.max_blocks, dev->num_cus - dev->reserve_cus, &p, &why))
+        return fail(rc, "rt_terrain_shade_rays: %s", why);
+    RtLaunch a = make_launch(dev, s);
+    a.consts = s->query.d_consts;
+    a.grad = s->query.d_grad;
+    RtShadeQuery q{};
+    q.rays = (const float4*)rays_device;
+    q.results = (float4*)results_device;
+    q.rgba8 = (uint32_t*)rgba8_device;
+    q.steps = (uint32_t*)steps_device;
+    q.n = (uint32_t)n;
+    memcpy(q.eye, eye, sizeof(eye));
+    q.blocks = p.blocks;
+    q.t_min = o.t_min;
+    q.t_max = o.t_max;
+    q.stepmod = o.stepmod;
+    q.max_steps = rtq::surface_max_steps(o.max_steps);
+    q.ray_range = (o.flags & rtq::kSurfRayRange) != 0;
+    if (!dev->rq_counter) HIP_TRY(hipMalloc(&dev->rq_counter, 64));
+    HIP_TRY(hipMemsetAsync(dev->rq_counter, 0, 4, dev->stream));
+    q.counter = dev->rq_counter;
+    if (!rt_launch_shadequery(a, q)) return fail(RT_ERR_UNSUPPORTED, "rt_terrain_shade_rays: no kernel for this query");
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+// the checks both forms share, in the order the header gives; *o: the parsed options
+int shade_rays_check(rt_compute c, int n, const rt_surface_options* opt, rtq::SurfOptions* o)
+{
+    if (!c) return fail(RT_ERR_INVALID, "null compute");
+    const char* why = "";
+    if (int rc = rtq::check_count(n, &why)) return fail(rc, "rt_terrain_shade_rays: %s", why);
+    if (int rc = rtq::parse_surface_options(opt, o, &why)) return fail(rc, "rt_terrain_shade_rays: %s", why);
+    if (!c->shader) return fail(RT_ERR_STATE, "no current shader");
+    if (c->shader->kind != KIND_TRACESCREEN)
+        return fail(RT_ERR_INVALID, "rt_terrain_shade_rays: a camerarays compute has no SunDirection; pass the tracescreen compute");
+    if (o->flags & rtq::kForceSegments)
+        return fail(RT_ERR_UNSUPPORTED, "rt_terrain_shade_rays: shaded queries have no segment shape");
+    return RT_OK;
+}
+
+} // namespace
+
+extern "C" int rt_terrain_shade_rays_device(rt_compute c, const void* rays_device, int n, const rt_surface_options* opt,
+                                            void* results_device, void* rgba8_device, void* steps_device)
+{
+    rtq::SurfOptions o;
+    if (int rc = shade_rays_check(c, n, opt, &o)) return rc;
+    if (n > 0 && !rays_device) return fail(RT_ERR_INVALID, "rt_terrain_shade_rays_device: null rays");
+    if (n > 0 && !results_device && !rgba8_device)
+        return fail(RT_ERR_INVALID, "rt_terrain_shade_rays_device: results and rgba8 are both null");
+    if (int rc = check_texture(c->shader)) return rc;
+    if (int rc = host_flag_check(c->dev)) return rc;
+    if (n == 0) return RT_OK;
+    HIP_TRY(hipSetDevice(c->dev->ordinal));
+    return shade_rays_enqueue(c, rays_device, n, o, results_device, rgba8_device, steps_device);
+}
+
+extern "C" int rt_terrain_shade_rays(rt_compute c, const float* origins, const float* dirs, const float* ranges, int n,
+                                     const rt_surface_options* opt, float* results, uint32_t* rgba8, uint32_t* steps)
+{
+    rtq::SurfOptions o;
+    if (int rc = shade_rays_check(c, n, opt, &o)) return rc;
+    if (n > 0 && (!origins || !dirs)) return fail(RT_ERR_INVALID, "rt_terrain_shade_rays: null origins or dirs");
+    if (n > 0 && !results && !rgba8) return fail(RT_ERR_INVALID, "rt_terrain_shade_rays: results and rgba8 are both null");
+    if (int rc = check_texture(c->shader)) return rc;
+    if (int rc = host_flag_check(c->dev)) return rc;
+    if (n == 0) return RT_OK;
+    // the host form packs the rays itself, so the spare words are the ranges exactly when it was given some
+    if (ranges) o.flags |= rtq::kSurfRayRange;
+    else o.flags &= ~rtq::kSurfRayRange;
+    rt_device dev = c->dev;
+    HIP_TRY(hipSetDevice(dev->ordinal));
+    // one device block: the packed rays, the results, the pixels, the step counts
+    const size_t nr = (size_t)n, rays_b = nr * 32, res_b = results ? nr * 32 : 0, px_b = rgba8 ? nr * 4 : 0,
+                 steps_b = steps ? nr * 8 : 0;
+    std::vector<float> packed(nr * 8);
+    rtq::pack(origins, dirs, n, packed.data());
+    if (ranges) rtq::pack_ranges(ranges, n, packed.data());
+    char* d = nullptr;
+    HIP_TRY(hipMalloc(&d, rays_b + res_b + px_b + steps_b));
+    char *d_res = d + rays_b, *d_px = d_res + res_b, *d_steps = d_px + px_b;
+    auto run = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(d, packed.data(), rays_b, hipMemcpyHostToDevice, dev->stream));
+        if (int rc = shade_rays_enqueue(c, d, n, o, results ? d_res : nullptr, rgba8 ? d_px : nullptr, steps ? d_steps : nullptr))
+            return rc;
+        if (results) HIP_TRY(hipMemcpyAsync(results, d_res, res_b, hipMemcpyDeviceToHost, dev->stream));
+        if (rgba8) HIP_TRY(hipMemcpyAsync(rgba8, d_px, px_b, hipMemcpyDeviceToHost, dev->stream));
+        if (steps) HIP_TRY(hipMemcpyAsync(steps, d_steps, steps_b, hipMemcpyDeviceToHost, dev->stream));
         HIP_TRY(hipStreamSynchronize(dev->stream));
         return RT_OK;
     };

@@ -815,8 +815,26 @@ __device__ __forceinline__ bool march_live(const Ctx& c, const March<L, CALCFOG>
     return m.dist < enddist && m.step > c.k->min_limit && !(max_steps > 0 && m.iters >= max_steps);
 }
 
-template <int L, bool CALCFOG, bool SKIPREFINE, class Density>
-__device__ __forceinline__ void march_step_with(const Ctx& c, March<L, CALCFOG>& m, Density density)
+// march_live with skiprefine per lane (march_step_with's run-time skip)
+template <int L, bool CALCFOG>
+__device__ __forceinline__ bool march_live_skip(const Ctx& c, const March<L, CALCFOG>& m, float enddist, int max_steps,
+                                                bool skip)
+{
+    if (skip && m.d > 0.0f) return false;
+    return march_live<L, CALCFOG, false>(c, m, enddist, max_steps);
+}
+
+// march_step_with's `skip` when nothing is passed: the compile-time SKIPREFINE, as a constant
+template <bool B>
+struct SkipConst {
+    __device__ constexpr operator bool() const { return B; }
+};
+
+// skip: skiprefine (tracing.hlsl:84).  By default the compile-time SKIPREFINE; a caller whose lanes march rays
+// of both kinds in one call (k_shadequery: refining primaries beside shadow rays) instantiates with
+// SKIPREFINE false and passes a bool per lane, and march_live_skip is its loop condition.
+template <int L, bool CALCFOG, bool SKIPREFINE, class Density, class Skip = SkipConst<SKIPREFINE>>
+__device__ __forceinline__ void march_step_with(const Ctx& c, March<L, CALCFOG>& m, Density density, Skip skip = Skip{})
 {
     const RtConsts* k = c.k;
     ++m.iters;
@@ -834,7 +852,7 @@ __device__ __forceinline__ void march_step_with(const Ctx& c, March<L, CALCFOG>&
     // without fog fs is +0 and m.f stays +0 (+0 + +0 == +0 - +0 == +0): no updates
     constexpr bool kFog = March<L, CALCFOG>::FOG;
     if (m.d > 0.0f) {
-        if constexpr (SKIPREFINE) return;
+        if (skip) return;
         m.dist = m.dist - m.lastStep;
         m.step = m.step * 0.3f;
         if constexpr (kFog) {

@@ -156,6 +156,16 @@
 #define RT_RAYQ_REFILL 56
 #endif
 
+// k_shadequery (the shaded queries): a wave visits its refill point -- where ended lanes are shaded and stored and
+// idle ones refilled -- once its live lanes are this many or fewer (at most 63).  Lower: the shading's heavy work
+// (normal, colour FBM, sky) runs on more lanes a visit, and the march on fewer.  The 2,073,600 pixel rays of the
+// 1920x1080 reset-pose frame, ms per query (lane utilisation of the march steps / of the shading visits): 56: 4.98
+// (80% / 13%), 48: 4.47 (78% / 20%), 40: 4.31 (76% / 28%), 32: 4.20 (71% / 35%), 24: 4.23 (68% / 44%), spreads 1-3%
+// (profiles/r11/shade_query.md).  k_rayquery's 56 leaves 8 lanes a visit for work worth several march steps.
+#ifndef RT_SHADEQ_REFILL
+#define RT_SHADEQ_REFILL 32
+#endif
+
 // (A/B) noise3d's z-layer replication t + Z * 0x01010101 as an inline v_mad_u32_u24
 #ifndef RT_Z_MAD24
 #define RT_Z_MAD24 0

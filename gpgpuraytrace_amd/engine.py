@@ -708,6 +708,53 @@ class Terrain:
                                                    results_ptr or None, steps_ptr or None)
         return rc == _native.RT_OK
 
+    def shade_rays(self, origins, dirs, ranges=None, eye=None, t_min=None, t_max=None, stepmod=None, max_steps=0,
+                   rgba8=False, steps=False, max_blocks=0):
+        """rt_terrain_shade_rays: what n rays of the caller's own LOOK like -- the sample tracescreen computes for
+        a pixel ray (tracescreen.hlsl:16-48): terrain colour with the sun's shadow, fog and sky, or the sky for a
+        miss.  One sample per ray and NO ambient occlusion, whatever the Terrain was built with.  origins, dirs,
+        ranges, t_min, t_max, stepmod, max_steps: as trace_surface.  eye: the density's LOD eye, getNormal's and
+        the sky's (default: the camera's).  The sun is the Terrain's (set_time_of_day).
+        Returns results (n, 8) float32 -- colour rgb (not saturated), distance | last sample xyz, density; a hit
+        is results[:, 7] > 0 -- or a tuple (results, [pixels (n,) uint32 RGBA8, R in the low byte, alpha 255, if
+        rgba8], [steps (n, 2) uint32: primary and shadow iterations, if steps]); None if the call fails
+        (lib().rt_last_error()).  max_blocks caps the persistent grid.  Blocking; uses the tracescreen compute;
+        needs set_camera() first."""
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise ValueError("shade_rays: %d origins, %d dirs" % (len(o), len(d)))
+        n = len(o)
+        rg = None
+        if ranges is not None:
+            rg = np.ascontiguousarray(ranges, np.float32).reshape(-1, 2)
+            if len(rg) != n:
+                raise ValueError("shade_rays: %d rays, %d ranges" % (n, len(rg)))
+        opt = surface_options(eye, "auto", max_blocks, t_min, t_max, stepmod, max_steps)
+        self.update_shaders()
+        res = np.empty((n, 8), np.float32)
+        px = np.empty(n, np.uint32) if rgba8 else None
+        st = np.empty((n, 2), np.uint32) if steps else None
+        rc = lib().rt_terrain_shade_rays(self.compute._h, o.ctypes.data, d.ctypes.data,
+                                         rg.ctypes.data if rg is not None else None, n, C.byref(opt), res.ctypes.data,
+                                         px.ctypes.data if rgba8 else None, st.ctypes.data if steps else None)
+        if rc != _native.RT_OK:
+            return None
+        out = (res,) + ((px,) if rgba8 else ()) + ((st,) if steps else ())
+        return out if len(out) > 1 else res
+
+    def shade_rays_device(self, rays_ptr, n, results_ptr=0, rgba8_ptr=0, steps_ptr=0, ray_range=False, eye=None,
+                          t_min=None, t_max=None, stepmod=None, max_steps=0, max_blocks=0):
+        """rt_terrain_shade_rays_device: the same for device arrays -- rays_ptr n x 8 float32 (pack_rays' layout;
+        with ray_range its spare words are the rays' ranges), results_ptr n x 8 float32 or 0, rgba8_ptr n uint32
+        or 0 (one of the two at least), steps_ptr n x 2 uint32 or 0 -- enqueued on the device's stream with no
+        host synchronisation.  True on success."""
+        opt = surface_options(eye, "auto", max_blocks, t_min, t_max, stepmod, max_steps, ray_range)
+        self.update_shaders()
+        rc = lib().rt_terrain_shade_rays_device(self.compute._h, rays_ptr or None, int(n), C.byref(opt),
+                                                results_ptr or None, rgba8_ptr or None, steps_ptr or None)
+        return rc == _native.RT_OK
+
 
 RAY_MODES ={"auto": 0, "segments": _native.RT_RAYS_FORCE_SEGMENTS, "lanes": _native.RT_RAYS_FORCE_LANES}
 

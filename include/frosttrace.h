@@ -502,6 +502,52 @@ int rt_terrain_trace_surface(rt_compute cs, const float* origins, const float* d
 int rt_terrain_trace_surface_device(rt_compute cs, const void* rays_device, int n,
                                     const rt_surface_options* opt, void* results_device, void* steps_device);
 
+/* ---- shaded queries (ABI 9, additive; no reference counterpart) ----
+ * What a ray of the host's own LOOKS like: terrain colour, sun shadow, fog and sky exactly as a frame shows them.
+ * Reflection and light probes, cube maps and panoramas, fisheye or off-axis cameras, the colour of a picked
+ * point.  For ray i with origin_i and dir_i and one eye E per call the result is what tracescreen.hlsl:16-48
+ * computes for one sample:
+ *     pdn   = normalize(dir_i)
+ *     rr    = traceRay(origin_i, t_min, t_max, stepmod, dir_i, calcfog ON, skiprefine OFF)       (cap: max_steps)
+ *     scat  = getRayleighMieColor(pdn);  skyAmount = saturate((rr.pd.w * 0.0005)^2)
+ *     hit   = rr.density > 0
+ *     hit : n = getNormal(float4(rr.pd.xyz, rr.density))
+ *           color = getColor(rr.pd.xyz, n, pdn, rr.pd.w)     (its shadow ray: traceRay(p, 0.4, 100,
+ *                                                    precision(rr.pd.w), SunDirection, fog ON, skiprefine ON))
+ *           color = lerp(lerp(color, rr.fcolord.rgb, rr.fcolord.w), scat.rayleigh, skyAmount)
+ *     miss: sky = scat.mie + scat.rayleigh + getSpaceColor(pdn)
+ *           color = lerp(lerp(sky, rr.fcolord.rgb, rr.fcolord.w), sky, skyAmount)
+ *     result_i = { float4(color.rgb, rr.pd.w), float4(rr.pd.xyz, rr.density) }     color NOT saturated
+ *     rgba8_i  = unorm8(saturate(color.rgb)), alpha 255       what a frame stores for a pixel of one sample
+ *     steps_i  = { primary iterations, shadow iterations (0 for a miss) }
+ *   dir   is used as given, as in the other queries: its LENGTH enters the first step (tracing.hlsl:54).
+ *   E     replaces Eye wherever the shaders read it: the density's level of detail, getNormal's eps and the sky.
+ *         Without RT_RAYS_EYE it is the compute's current Eye variable.  One per call.
+ *   SunDirection, RECORDING and the landscape constants come from the compute, which must be a TRACESCREEN
+ *         compute (camerarays has no SunDirection).  Its AA_SAMPLES, RT_MAX_STEPS and RT_AO_SAMPLES macros are
+ *         ignored: one sample per ray, the option block's max_steps is the cap.
+ *   NO ambient occlusion: the result is the sample before any AO factor, whatever the compute was built with.
+ *         Nor a segment shape or a sun per ray; the option block's size field leaves room for them later.
+ *   A zero dir or non-finite inputs give unspecified results; the kernel still ends.
+ * The option block is rt_surface_options, parsed as for the surface queries: RT_RAYS_EYE, RT_SURFACE_PARAMS
+ *   (t_min, t_max, stepmod, max_steps; defaults 0.01, 5000, 1, unbounded), RT_SURFACE_RAY_RANGE and max_blocks
+ *   mean what they mean there.  There is one kernel shape, the lanes': RT_RAYS_FORCE_LANES changes nothing and
+ *   RT_RAYS_FORCE_SEGMENTS is RT_ERR_UNSUPPORTED.
+ * rt_terrain_shade_rays: host arrays (origins, dirs: 3n floats; ranges: 2n floats or NULL; results: 8n floats or
+ *   NULL; rgba8: n uint32 (R in the low byte) or NULL; steps: 2n uint32 or NULL); blocking.
+ * rt_terrain_shade_rays_device: device arrays (rays n x 8 floats, 16-byte aligned; results n x 8 floats, 16-byte
+ *   aligned, or NULL; rgba8 n uint32 or NULL; steps 2n uint32 or NULL), enqueued on the compute's device stream
+ *   with no host synchronisation.
+ * Both: at least one of results and rgba8.  n == 0 is RT_OK and launches nothing.  RT_ERR_INVALID: n < 0,
+ *   n > 2^26, a NULL compute or rays, results and rgba8 both NULL, the option block's errors as above, a
+ *   camerarays compute.  RT_ERR_STATE without texPerm2D bound, or with the fail-safe word set.  A query reads no
+ *   frame state and changes none: it flushes no deferred frame, invalidates no ahead / fused prepass or captured
+ *   graph, and uploads the constants it needs to a copy of its own, so it may run between any two renders. */
+int rt_terrain_shade_rays(rt_compute screen_cs, const float* origins, const float* dirs, const float* ranges, int n,
+                          const rt_surface_options* opt, float* results, uint32_t* rgba8, uint32_t* steps);
+int rt_terrain_shade_rays_device(rt_compute screen_cs, const void* rays_device, int n, const rt_surface_options* opt,
+                                 void* results_device, void* rgba8_device, void* steps_device);
+
 /* ---- diagnostics (primitive-level parity tests; no reference counterpart) ----
  * rt_debug_math: device evaluation of the numeric primitives of DESIGN.md §Numerics
  *   (op 0 exp2, 1 log2, 2 exp, 3 sin, 4 cos, 5 sqrt, 6 rcp, 7 rsqrt, 8 pow, 9 max,
