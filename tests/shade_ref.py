@@ -38,7 +38,7 @@ def lib():
         L = C.CDLL(SO)
         fp = C.POINTER(C.c_float)
         L.sr_shade_rays.argtypes = [C.POINTER(O.Noise), C.POINTER(O.Frame), fp, fp, fp, C.c_int64, C.c_float,
-                                    C.c_float, C.c_float, C.c_int, fp, C.c_void_p, C.c_void_p, C.c_void_p, fp]
+                                    C.c_float, C.c_float, C.c_int, fp, C.c_void_p, C.c_void_p, C.c_void_p, fp, fp]
         L.sr_shade_rays.restype = None
         L.sr_trace_sample.argtypes = [C.POINTER(O.Noise), C.POINTER(O.Frame), fp, fp, fp, C.c_int64, C.c_float,
                                       C.c_float, fp, C.c_void_p]
@@ -65,9 +65,10 @@ def _rays(origins, dirs, ranges):
 
 
 def shade(origins, dirs, eye, landscape, ranges=None, t_min=T_MIN, t_max=T_MAX, stepmod=1.0, max_steps=0, recording=0,
-          sun=SUN):
+          sun=SUN, fog_rgb=False):
     """(results (n, 8) float32, rgba8 (n,) uint32, steps (n, 2) uint32, classes (n,) uint8: MISS, LIT, SHADOWED,
-    fog_w (n,) float32: the primary march's fcolord.w) of the definition in include/frosttrace.h for these rays."""
+    fog_w (n,) float32: the primary march's fcolord.w) of the definition in include/frosttrace.h for these rays;
+    with fog_rgb a sixth: (n, 3) float32, the primary march's fcolord.rgb."""
     o, d, rg = _rays(origins, dirs, ranges)
     n = len(o)
     fr = frame(eye, landscape, sun, recording)
@@ -76,10 +77,11 @@ def shade(origins, dirs, eye, landscape, ranges=None, t_min=T_MIN, t_max=T_MAX, 
     steps = np.zeros((n, 2), np.uint32)
     cls = np.zeros(n, np.uint8)
     fog = np.zeros(n, np.float32)
+    frgb = np.zeros((n, 3), np.float32) if fog_rgb else None
     lib().sr_shade_rays(C.byref(O.noise_tables()), C.byref(fr), O._fp(o), O._fp(d), O._fp(rg) if rg is not None else None,
                         n, t_min, t_max, stepmod, max_steps, O._fp(res), px.ctypes.data, steps.ctypes.data, cls.ctypes.data,
-                        O._fp(fog))
-    return res, px, steps, cls, fog
+                        O._fp(fog), O._fp(frgb) if fog_rgb else None)
+    return (res, px, steps, cls, fog, frgb) if fog_rgb else (res, px, steps, cls, fog)
 
 
 def trace_sample(origins, dirs, eye, landscape, ranges=None, t_min=T_MIN, t_max=T_MAX, max_steps=0, recording=0, sun=SUN):

@@ -1,0 +1,86 @@
+"""The oracle's shading stages at inputs of the caller's own (TEST INFRASTRUCTURE): builds, binds and caches
+tests/tools/stage_ref.c, which includes the oracle's source and exports its static get_normal, get_fog,
+get_pixel_ray and get_color.  Built with the oracle's own flags into tests/tools/_build/."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+import oracle_lib as O
+import shade_ref as SH
+import surface_ref as SR
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "tests", "tools", "stage_ref.c")
+SO = os.path.join(ROOT, "tests", "tools", "_build", "libstage_ref.so")
+LIT, SHADOWED = SH.LIT, SH.SHADOWED
+
+_lib = None
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        deps = [SRC, os.path.join(ROOT, "oracle", "rt_oracle.c"), os.path.join(ROOT, "oracle", "rt_oracle.h")]
+        if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(p) for p in deps):
+            os.makedirs(os.path.dirname(SO), exist_ok=True)
+            tmp = "%s.%d.tmp" % (SO, os.getpid())
+            subprocess.run(["gcc"] + SR.CFLAGS + ["-shared", "-o", tmp, SRC, "-lm"], check=True)
+            os.replace(tmp, SO)
+        L = C.CDLL(SO)
+        fp, nzp, frp = C.POINTER(C.c_float), C.POINTER(O.Noise), C.POINTER(O.Frame)
+        L.st_normal.argtypes = [nzp, frp, fp, C.c_int64, fp]
+        L.st_fog.argtypes = [nzp, frp, fp, fp, C.c_int64, fp]
+        L.st_pixel_ray.argtypes = [nzp, frp, fp, C.c_int64, fp, fp]
+        L.st_color.argtypes = [nzp, frp, fp, fp, fp, fp, C.c_int64, fp, C.c_void_p, fp]
+        for f in (L.st_normal, L.st_fog, L.st_pixel_ray, L.st_color):
+            f.restype = None
+        _lib = L
+    return _lib
+
+
+def _a(x, width):
+    return np.ascontiguousarray(x, np.float32).reshape(-1, width)
+
+
+def normal(land, pos, w, eye):
+    """get_normal(float4(pos, w)) with Eye = eye: (n, 3) float32."""
+    pd = np.ascontiguousarray(np.concatenate([_a(pos, 3), _a(w, 1)], axis=1), np.float32)
+    out = np.zeros((len(pd), 3), np.float32)
+    fr = SH.frame(eye, land)
+    lib().st_normal(C.byref(O.noise_tables()), C.byref(fr), O._fp(pd), len(pd), O._fp(out))
+    return out
+
+
+def fog(land, p, dist):
+    """get_fog(p, dist): (n, 4) float32."""
+    p, dist = _a(p, 3), _a(dist, 1)
+    assert len(p) == len(dist)
+    out = np.zeros((len(p), 4), np.float32)
+    fr = SH.frame((0, 0, 0), land)
+    lib().st_fog(C.byref(O.noise_tables()), C.byref(fr), O._fp(p), O._fp(dist), len(p), O._fp(out))
+    return out
+
+
+def pixel_ray(consts, px, py):
+    """get_pixel_ray for the frame constants (oracle_lib.make_frame's dict): (p (n, 3), dir (n, 3)) float32."""
+    pix = np.ascontiguousarray(np.stack([np.asarray(px, np.float32).ravel(), np.asarray(py, np.float32).ravel()], axis=1))
+    p, d = np.zeros((len(pix), 3), np.float32), np.zeros((len(pix), 3), np.float32)
+    fr = O.make_frame(consts)
+    lib().st_pixel_ray(C.byref(O.noise_tables()), C.byref(fr), O._fp(pix), len(pix), O._fp(p), O._fp(d))
+    return p, d
+
+
+def color(land, p, n, d, dist, eye, sun=SH.SUN):
+    """get_color(p, n, d, dist) with SunDirection = sun and Eye = eye (the shadow march's level of detail):
+    (rgb (n, 3) float32, classes (n,) uint8: LIT or SHADOWED, the shadow ray's fcolord.w (n,) float32)."""
+    p, n, d, dist = _a(p, 3), _a(n, 3), _a(d, 3), _a(dist, 1)
+    assert len(p) == len(n) == len(d) == len(dist)
+    rgb = np.zeros((len(p), 3), np.float32)
+    cls = np.zeros(len(p), np.uint8)
+    w = np.zeros(len(p), np.float32)
+    fr = SH.frame(eye, land, sun)
+    lib().st_color(C.byref(O.noise_tables()), C.byref(fr), O._fp(p), O._fp(n), O._fp(d), O._fp(dist), len(p), O._fp(rgb),
+                   cls.ctypes.data, O._fp(w))
+    return rgb, cls, w

@@ -10,7 +10,8 @@
  * fr->aa_samples, fr->max_steps and fr->ao_samples are not read.
  * results: 8 floats a ray (colour rgb NOT saturated, pd.w | pd.xyz, density); rgba8: unorm8(saturate(colour)),
  * R in the low byte, alpha 255; steps: 2 a ray (primary, shadow iterations).  For the tests' own census, each
- * optional: classes (0 a miss, 1 a lit hit, 2 a shadowed hit) and fog_w (the primary march's fcolord.w).
+ * optional: classes (0 a miss, 1 a lit hit, 2 a shadowed hit), fog_w (the primary march's fcolord.w) and fog_rgb
+ * (3 a ray: its fcolord.rgb).
  *
  * sr_trace_sample is the oracle's own trace_sample (tracescreen.hlsl:16-48) for the same rays, stepmod 1 as it
  * has it, with fr->ao_samples = 0 and fr->max_steps as the cap: what pins sr_shade_rays.
@@ -19,7 +20,7 @@
 
 void sr_shade_rays(const ro_noise* nz, const ro_frame* fr, const float* origins, const float* dirs,
                    const float* ranges, int64_t n, float t_min, float t_max, float stepmod, int max_steps,
-                   float* results, uint32_t* rgba8, uint32_t* steps, uint8_t* classes, float* fog_w)
+                   float* results, uint32_t* rgba8, uint32_t* steps, uint8_t* classes, float* fog_w, float* fog_rgb)
 {
     sky_consts k;
     sky_init(&k);
@@ -60,6 +61,7 @@ void sr_shade_rays(const ro_noise* nz, const ro_frame* fr, const float* origins,
         steps[2 * i] = (uint32_t)rr.steps;
         steps[2 * i + 1] = (uint32_t)shadow;
         if (fog_w) fog_w[i] = rr.fcolord.w; /* the primary's */
+        if (fog_rgb) { fog_rgb[3 * i] = rr.fcolord.x; fog_rgb[3 * i + 1] = rr.fcolord.y; fog_rgb[3 * i + 2] = rr.fcolord.z; }
         if (classes) { /* 0 a miss, 1 a lit hit, 2 a shadowed hit: get_color's shadow ray once more */
             classes[i] = 0;
             if (rr.density > 0.0f) {
