@@ -55,6 +55,18 @@ class RtSurfaceOptions(C.Structure):
                 ("t_min", C.c_float), ("t_max", C.c_float), ("stepmod", C.c_float), ("max_steps", C.c_uint32)]
 
 
+RT_FIELD_NORMAL = 32  # rt_field_options.flags beside RT_RAYS_EYE: results are float4 {normal, density}
+RT_MAX_LATTICE_DIM = 4096
+
+
+class RtFieldOptions(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("eye", C.c_float * 3), ("max_blocks", C.c_uint32)]
+
+
+class RtLattice(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("spacing", C.c_float * 3), ("dims", C.c_uint32 * 3)]
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -137,6 +149,11 @@ SIGNATURES = {
     # shaded queries (one sample a ray, no AO): the tracescreen compute; results (8n floats), rgba8 (n), steps (2n)
     "rt_terrain_shade_rays": (_i, [_vp, _vp, _vp, _vp, _i, C.POINTER(RtSurfaceOptions), _vp, _vp, _vp]),
     "rt_terrain_shade_rays_device": (_i, [_vp, _vp, _i, C.POINTER(RtSurfaceOptions), _vp, _vp, _vp]),
+    # field queries: density (and normal) at points (n x 3 host, n x 4 device) and on a lattice (+ occupancy bits)
+    "rt_terrain_sample_field": (_i, [_vp, _vp, _i, C.POINTER(RtFieldOptions), _vp]),
+    "rt_terrain_sample_field_device": (_i, [_vp, _vp, _i, C.POINTER(RtFieldOptions), _vp]),
+    "rt_terrain_sample_lattice": (_i, [_vp, C.POINTER(RtLattice), C.POINTER(RtFieldOptions), _vp, _vp]),
+    "rt_terrain_sample_lattice_device": (_i, [_vp, C.POINTER(RtLattice), C.POINTER(RtFieldOptions), _vp, _vp]),
     "rt_noise_generate": (_i, [C.c_uint32, _i, _vp, _vp]),
     "rt_terrain_set_target_depths": (_i, [_vp, _vp]),
     "rt_recorder_create": (_i, [_vp, _i, _i, _cp, C.POINTER(_vp)]),

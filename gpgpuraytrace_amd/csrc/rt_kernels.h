@@ -183,6 +183,28 @@ struct RtShadeQuery {
 };
 bool rt_launch_shadequery(const RtLaunch& a, const RtShadeQuery& q);
 
+// A field query (rt_terrain_sample_field / rt_terrain_sample_lattice): getDensity, with `normal` also getNormal
+// (tracing.hlsl:107-116, for every point), with the launch's landscape, noise tables and constants and `eye` in
+// place of Eye.  points set: n points x y z _ (one float4 each) -> results[n], float or with `normal` float4
+// {n.xyz, d}.  points null: the lattice of dims points at fmaf(i, spacing, origin), n their product, result index
+// (iz * ny + iy) * nx + ix -> results (may be null) and occupancy (may be null; d > 0, one bit a point,
+// ceil(nx / 32) words a row), in strips of 64 ix by `rows` iy; `column`: nomadplains' steep noise once per strip
+// column.  `blocks` blocks of 1024 threads stride over the work.  false: no such kernel (nothing launched).
+struct RtFieldQuery {
+    const float4* points;
+    void* results;
+    uint32_t* occupancy;
+    uint32_t n;
+    float eye[3];
+    bool normal;
+    uint32_t blocks;
+    float origin[3], spacing[3];
+    uint32_t dims[3];
+    uint32_t rows;
+    bool column;
+};
+bool rt_launch_fieldquery(const RtLaunch& a, const RtFieldQuery& q);
+
 #define RT_TILE 32
 #define RT_FIN_SLOTS 1536 // k_trace's fin pool slots per block
 #define RT_AO_POOL_SLOTS 256 // k_trace's AO counter slots per block (LDS) and their colours (cpool)

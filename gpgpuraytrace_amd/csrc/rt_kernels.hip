@@ -3078,6 +3078,148 @@ bool rt_launch_shadequery(const RtLaunch& a, const RtShadeQuery& q)
 }
 
 // ---------------------------------------------------------------------------
+// Field queries (rt_terrain_sample_field, rt_terrain_sample_lattice): getDensity, and with NORMAL getNormal
+// (tracing.hlsl:107-116, for every point, inside or outside), at points instead of along rays.  The eye (nomadplains'
+// octave count, getNormal's eps) is a kernel argument, as in the ray queries.  A point's result is one float, or with
+// NORMAL one float4 {n.xyz, d}.  One 1024-thread block per CU at most (the noise tables fill its LDS); a block
+// strides over the work, so the tables are loaded once per block whatever the size of the query.
+namespace {
+
+struct FieldEye {
+    float x, y, z;
+};
+
+template <int L, bool NORMAL>
+__device__ __forceinline__ void store_field_result(const Ctx& c, f3 p, float d, void* __restrict__ out, uint32_t i)
+{
+    if constexpr (NORMAL) {
+        const f3 nrm = get_normal<L>(c, f4{p.x, p.y, p.z, d});
+        gstore((float4*)out + i, make_float4(nrm.x, nrm.y, nrm.z, d));
+    } else {
+        ((float*)out)[i] = d;
+    }
+}
+
+// Points from memory: point i is one 16-byte load (x y z _), tiles of 1024 consecutive points dealt to the blocks
+// round robin.  n <= 2^26.
+template <int L, bool NORMAL>
+__global__ void __launch_bounds__(1024) k_fieldpoints(const RtConsts* __restrict__ k, const uint32_t* __restrict__ perm2d,
+                                                      const float4* __restrict__ grad,
+                                                      const float4* __restrict__ points, void* __restrict__ out,
+                                                      uint32_t n, FieldEye e)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t lds[kNoiseLdsWords];
+    load_noise_lds(lds, perm2d, grad, k);
+    Ctx c = make_ctx(k, lds);
+    c.eye = rtm::mk(e.x, e.y, e.z);
+    const uint32_t tiles = (n + 1023u) / 1024u;
+    for (uint32_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const uint32_t i = t * 1024u + threadIdx.x;
+        if (i < n) {
+            const float4 q = points[i];
+            const f3 p = rtm::mk(q.x, q.y, q.z);
+            store_field_result<L, NORMAL>(c, p, get_density<L>(c, p), out, i);
+        }
+    }
+}
+
+// A lattice: point (ix, iy, iz) at fmaf(i, spacing, origin) per axis, result index (iz * ny + iy) * nx + ix; no
+// coordinates are read.  A wave takes strips of 64 consecutive ix by `rows` consecutive iy of one iz and walks
+// them in y: its stores are whole rows, its hit ballot is the strip row's two occupancy words (each written once,
+// whole, by one lane), and all its lanes share y, so the wave tests of the density (terraces, floor lift, pow)
+// skip as often as they can.  With COLUMN (nomadplains) a lane computes the steep noise of its (ix, iz) column
+// once per strip.  nx * ny * nz <= 2^26; out or occ may be null (not both).
+struct FieldLattice {
+    float ox, oy, oz, sx, sy, sz;
+    uint32_t nx, ny, nz, rows;
+};
+
+template <int L, bool NORMAL, bool COLUMN>
+__global__ void __launch_bounds__(1024) k_fieldlattice(const RtConsts* __restrict__ k, const uint32_t* __restrict__ perm2d,
+                                                       const float4* __restrict__ grad, void* __restrict__ out,
+                                                       uint32_t* __restrict__ occ, FieldLattice g, FieldEye e)
+{
+    static_assert(!COLUMN || L == RT_NOMADPLAINS, "the column shape is nomadplains'");
+    __shared__ __attribute__((aligned(16))) uint32_t lds[kNoiseLdsWords];
+    load_noise_lds(lds, perm2d, grad, k);
+    Ctx c = make_ctx(k, lds);
+    c.eye = rtm::mk(e.x, e.y, e.z);
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
+    const uint32_t xc = (g.nx + 63u) / 64u, yc = (g.ny + g.rows - 1u) / g.rows, strips = xc * yc * g.nz;
+    const uint32_t words = (g.nx + 31u) / 32u; // occupancy words per (iy, iz) row
+    for (uint32_t s = blockIdx.x * waves + wave; s < strips; s += gridDim.x * waves) {
+        const uint32_t cx = s % xc, r = s / xc, cy = r % yc, iz = r / yc;
+        const uint32_t ix = cx * 64u + lane, iy0 = cy * g.rows, iy1 = iy0 + g.rows < g.ny ? iy0 + g.rows : g.ny;
+        const bool valid = ix < g.nx;
+        const float px = fmaf((float)ix, g.sx, g.ox), pz = fmaf((float)iz, g.sz, g.oz);
+        float sn = 0.0f;
+        if constexpr (COLUMN) {
+            if (valid) sn = np_steep_noise(c, rtm::mk(px, 0.0f, pz));
+        }
+        for (uint32_t iy = iy0; iy < iy1; ++iy) {
+            const uint32_t row = iz * g.ny + iy;
+            float d = 0.0f;
+            if (valid) {
+                const f3 p = rtm::mk(px, fmaf((float)iy, g.sy, g.oy), pz);
+                if constexpr (COLUMN) d = density_nomadplains_column(c, p, sn);
+                else d = get_density<L>(c, p);
+                if (out) store_field_result<L, NORMAL>(c, p, d, out, row * g.nx + ix);
+            }
+            if (occ) {
+                const uint64_t hit = __ballot(valid && d > 0.0f); // tracescreen.hlsl:29
+                const uint32_t w = cx * 2u + (lane >> 5);
+                if ((lane & 31u) == 0u && w < words) occ[(size_t)row * words + w] = (uint32_t)(hit >> (lane & 32u));
+            }
+        }
+    }
+}
+
+template <int L, bool NORMAL>
+void launch_fieldquery(const RtLaunch& a, const RtFieldQuery& q)
+{
+    const FieldEye e{q.eye[0], q.eye[1], q.eye[2]};
+    if (q.points) {
+        hipLaunchKernelGGL((k_fieldpoints<L, NORMAL>), dim3(q.blocks), dim3(1024), 0, a.stream, a.consts, a.perm2d,
+                           a.grad, q.points, q.results, q.n, e);
+        return;
+    }
+    const FieldLattice g{q.origin[0], q.origin[1], q.origin[2], q.spacing[0], q.spacing[1], q.spacing[2],
+                         q.dims[0],   q.dims[1],   q.dims[2],   RT_FIELD_ROWS > 0 ? (uint32_t)RT_FIELD_ROWS : q.rows};
+    if constexpr (L == RT_NOMADPLAINS) {
+        if (q.column && RT_FIELD_COLUMN) {
+            hipLaunchKernelGGL((k_fieldlattice<L, NORMAL, true>), dim3(q.blocks), dim3(1024), 0, a.stream, a.consts,
+                               a.perm2d, a.grad, q.results, q.occupancy, g, e);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((k_fieldlattice<L, NORMAL, false>), dim3(q.blocks), dim3(1024), 0, a.stream, a.consts, a.perm2d,
+                       a.grad, q.results, q.occupancy, g, e);
+}
+
+template <int L>
+void launch_fieldquery_l(const RtLaunch& a, const RtFieldQuery& q)
+{
+    // occupancy alone needs no normal
+    if (q.normal && q.results) launch_fieldquery<L, true>(a, q);
+    else launch_fieldquery<L, false>(a, q);
+}
+
+} // namespace
+
+bool rt_launch_fieldquery(const RtLaunch& a, const RtFieldQuery& q)
+{
+    if (q.n == 0 || q.blocks == 0) return true;
+    if (q.points ? !q.results : ((!q.results && !q.occupancy) || q.rows == 0)) return false;
+    switch (a.landscape) {
+    case RT_TESTING: launch_fieldquery_l<RT_TESTING>(a, q); break;
+    case RT_SIMPLE: launch_fieldquery_l<RT_SIMPLE>(a, q); break;
+    case RT_GREENROCKS: launch_fieldquery_l<RT_GREENROCKS>(a, q); break;
+    default: launch_fieldquery_l<RT_NOMADPLAINS>(a, q); break;
+    }
+    return true;
+}
+
+// ---------------------------------------------------------------------------
 // Diagnostics: device evaluation of the numeric primitives, noise3d and
 // getDensity for the primitive-level parity tests (tests/test_gpu_parity.py).
 namespace {

@@ -1,7 +1,8 @@
-// rt_rayquery.h -- host-only decisions of rt_terrain_trace_rays, rt_terrain_trace_surface and
-// rt_terrain_shade_rays (include/frosttrace.h): the option blocks' validation and the choice of the kernel
-// shape, its lanes per ray and its grid.  No HIP in here: tests/tools/rayquery_check.cpp, surfquery_check.cpp
-// and shadequery_check.cpp drive it stand-alone under ASan + UBSan.
+// rt_rayquery.h -- host-only decisions of rt_terrain_trace_rays, rt_terrain_trace_surface,
+// rt_terrain_shade_rays and the field queries rt_terrain_sample_field / rt_terrain_sample_lattice
+// (include/frosttrace.h): the option blocks' validation and the choice of the kernel shape, its lanes per ray,
+// its strips and its grid.  No HIP in here: tests/tools/rayquery_check.cpp, surfquery_check.cpp,
+// shadequery_check.cpp and fieldquery_check.cpp drive it stand-alone under ASan + UBSan.
 #pragma once
 
 #include <cstddef>
@@ -205,6 +206,133 @@ inline int plan_shade(int n, uint32_t flags, uint32_t max_blocks, int cus, Plan*
         return UNSUPPORTED;
     }
     return plan(n, false, kForceLanes, max_blocks, cus, 0, 0, out, why);
+}
+
+// ---- field queries (rt_terrain_sample_field, rt_terrain_sample_lattice): density and normal at points ----
+
+// rt_field_options.flags beside kEye (RT_FIELD_NORMAL); every other bit is an error
+constexpr uint32_t kFieldNormal = 32u;
+// the first version of rt_field_options: size, flags, eye[3], max_blocks
+constexpr uint32_t kFieldOptSizeV1 = 24u;
+constexpr uint32_t kMaxLatticeDim = 4096u;
+// iy rows of a lattice strip (k_fieldlattice: a wave walks 64 ix by this many iy of one iz, and on nomadplains
+// computes its columns' steep noise once per strip).  Measured on a 256 x 128 x 256 lattice
+// (profiles/r12/field_query.md): 0.2187 ms at 1 row, 0.2052 at 4, 0.2034 at 8, 0.2048 at 16, 0.2119 at 32;
+// 0.2065 at 8 rows without the column reuse; the point form 0.2113.
+constexpr uint32_t kFieldRows = 8u;
+// waves of a field kernel's block (1024 threads)
+constexpr uint32_t kFieldWaves = 16u;
+
+struct FieldOptions {
+    uint32_t flags = 0;
+    float eye[3] = {0.0f, 0.0f, 0.0f};
+    uint32_t max_blocks = 0;
+};
+
+// `opt` is the caller's rt_field_options (may be null: the defaults), read through its size field only as far
+// as the first version reaches.
+inline int parse_field_options(const void* opt, FieldOptions* out, const char** why)
+{
+    *out = FieldOptions{};
+    if (!opt) return OK;
+    uint32_t size;
+    std::memcpy(&size, opt, 4);
+    if (size < kFieldOptSizeV1) {
+        *why = "rt_field_options.size is smaller than the struct's first version";
+        return INVALID;
+    }
+    const char* p = static_cast<const char*>(opt);
+    std::memcpy(&out->flags, p + 4, 4);
+    std::memcpy(out->eye, p + 8, 12);
+    std::memcpy(&out->max_blocks, p + 20, 4);
+    if (out->flags & ~(kEye | kFieldNormal)) {
+        *why = "rt_field_options.flags has bits other than RT_RAYS_EYE and RT_FIELD_NORMAL";
+        return INVALID;
+    }
+    return OK;
+}
+
+struct Lattice {
+    float origin[3], spacing[3];
+    uint32_t dims[3];
+};
+
+// `lat` is the caller's rt_lattice (36 bytes); *n: its points (0: nothing to do)
+inline int check_lattice(const void* lat, Lattice* out, uint32_t* n, const char** why)
+{
+    if (!lat) {
+        *why = "null rt_lattice";
+        return INVALID;
+    }
+    std::memcpy(out, lat, sizeof(Lattice));
+    uint64_t total = 1;
+    for (int i = 0; i < 3; ++i) {
+        if (out->dims[i] > kMaxLatticeDim) {
+            *why = "a lattice dimension is above 4096";
+            return INVALID;
+        }
+        if (!finite_f(out->origin[i]) || !finite_f(out->spacing[i])) {
+            *why = "the lattice's origin and spacing must be finite";
+            return INVALID;
+        }
+        total *= out->dims[i];
+    }
+    if (total > (uint64_t)kMaxRays) {
+        *why = "the lattice has more than 2^26 points";
+        return INVALID;
+    }
+    *n = (uint32_t)total;
+    return OK;
+}
+
+struct FieldPlan {
+    uint32_t blocks = 0; // of 1024 threads, striding over the work
+    uint32_t rows = 1;   // (lattice) iy rows per strip
+    bool column = false; // (lattice) nomadplains' steep noise once per strip column
+};
+
+inline uint32_t field_grid(uint32_t need, uint32_t max_blocks, int cus)
+{
+    uint32_t b = (uint32_t)(cus > 0 ? cus : 1);
+    if (max_blocks && max_blocks < b) b = max_blocks;
+    return need < b ? need : b;
+}
+
+// n >= 1 points from memory: tiles of 1024, grid min(tiles, cus, max_blocks)
+inline FieldPlan plan_field_points(uint32_t n, uint32_t max_blocks, int cus)
+{
+    FieldPlan p;
+    p.blocks = field_grid((n + 1023u) / 1024u, max_blocks, cus);
+    return p;
+}
+
+// strips of a lattice whose dims are all >= 1: 64 ix by `rows` iy of one iz
+inline uint32_t lattice_strips(const uint32_t dims[3], uint32_t rows)
+{
+    return ((dims[0] + 63u) / 64u) * ((dims[1] + rows - 1u) / rows) * dims[2];
+}
+
+// a lattice of >= 1 points (check_lattice passed): grid min(ceil(strips / 16), cus, max_blocks)
+inline FieldPlan plan_field_lattice(const uint32_t dims[3], bool nomadplains, uint32_t max_blocks, int cus)
+{
+    FieldPlan p;
+    p.rows = dims[1] < kFieldRows ? dims[1] : kFieldRows;
+    p.column = nomadplains && p.rows > 1u;
+    const uint32_t strips = lattice_strips(dims, p.rows);
+    p.blocks = field_grid((strips + kFieldWaves - 1u) / kFieldWaves, max_blocks, cus);
+    return p;
+}
+
+// point i of a packed field query: x y z _
+inline void pack_points(const float* points, int n, float* packed)
+{
+    for (int i = 0; i < n; ++i) {
+        float* r = packed + (size_t)i * 4;
+        r[0] = points[3 * (size_t)i];
+        r[1] = points[3 * (size_t)i + 1];
+        r[2] = points[3 * (size_t)i + 2];
+        r[3] = 0.0f;
+    }
 }
 
 // ray i of a packed query with its range: ox oy oz t_min_i dx dy dz t_max_i (ranges: 2n floats)

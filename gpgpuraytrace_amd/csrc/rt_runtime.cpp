@@ -3117,6 +3117,166 @@ extern "C" int rt_terrain_shade_rays(rt_compute c, const float* origins, const f
 }
 
 // ---------------------------------------------------------------------------
+// rt_terrain_sample_field / rt_terrain_sample_lattice: the density field and its normal at points and on a lattice
+// (include/frosttrace.h).  The query state (Shader::query) is the ray queries'; the eye is a kernel argument.
+namespace {
+
+// enqueue one field query of n >= 1 points on the device stream (no host synchronisation); lat null: points
+int sample_field_enqueue(rt_compute c, const void* points_device, const rtq::Lattice* lat, uint32_t n,
+                         const rtq::FieldOptions& o, void* results_device, void* occupancy_device)
+{
+    rt_device dev = c->dev;
+    Shader* s = c->shader;
+    float eye[3];
+    if (int rc = sync_query_consts(dev, s, eye)) return rc;
+    if (o.flags & rtq::kEye) memcpy(eye, o.eye, sizeof(eye));
+    const int cus = dev->num_cus - dev->reserve_cus;
+    RtLaunch a = make_launch(dev, s);
+    a.consts = s->query.d_consts;
+    a.grad = s->query.d_grad;
+    RtFieldQuery q{};
+    q.points = (const float4*)points_device;
+    q.results = results_device;
+    q.occupancy = (uint32_t*)occupancy_device;
+    q.n = n;
+    memcpy(q.eye, eye, sizeof(eye));
+    q.normal = (o.flags & rtq::kFieldNormal) != 0;
+    rtq::FieldPlan p;
+    if (lat) {
+        p = rtq::plan_field_lattice(lat->dims, s->landscape == RT_NOMADPLAINS, o.max_blocks, cus);
+        memcpy(q.origin, lat->origin, sizeof(q.origin));
+        memcpy(q.spacing, lat->spacing, sizeof(q.spacing));
+        memcpy(q.dims, lat->dims, sizeof(q.dims));
+    } else {
+        p = rtq::plan_field_points(n, o.max_blocks, cus);
+    }
+    q.blocks = p.blocks;
+    q.rows = p.rows;
+    q.column = p.column;
+    if (!rt_launch_fieldquery(a, q)) return fail(RT_ERR_UNSUPPORTED, "field query: no kernel for this query");
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+// the checks every form shares, in the order the header gives; *o: the parsed options
+int sample_field_check(rt_compute c, const rt_field_options* opt, rtq::FieldOptions* o, const char* who)
+{
+    if (!c) return fail(RT_ERR_INVALID, "null compute");
+    const char* why = "";
+    if (int rc = rtq::parse_field_options(opt, o, &why)) return fail(rc, "%s: %s", who, why);
+    if (!c->shader) return fail(RT_ERR_STATE, "no current shader");
+    return RT_OK;
+}
+
+int sample_lattice_check(rt_compute c, const rt_lattice* lat, const rt_field_options* opt, rtq::FieldOptions* o,
+                         rtq::Lattice* l, uint32_t* n, const void* results, const void* occupancy, const char* who)
+{
+    if (int rc = sample_field_check(c, opt, o, who)) return rc;
+    const char* why = "";
+    if (int rc = rtq::check_lattice(lat, l, n, &why)) return fail(rc, "%s: %s", who, why);
+    if (*n > 0 && !results && !occupancy) return fail(RT_ERR_INVALID, "%s: results and occupancy are both null", who);
+    if (int rc = check_texture(c->shader)) return rc;
+    return host_flag_check(c->dev);
+}
+
+// a field result's bytes per point
+size_t field_stride(const rtq::FieldOptions& o) { return (o.flags & rtq::kFieldNormal) ? 16 : 4; }
+
+} // namespace
+
+extern "C" int rt_terrain_sample_field_device(rt_compute c, const void* points_device, int n, const rt_field_options* opt,
+                                              void* results_device)
+{
+    rtq::FieldOptions o;
+    const char* why = "";
+    if (!c) return fail(RT_ERR_INVALID, "null compute");
+    if (int rc = rtq::check_count(n, &why)) return fail(rc, "rt_terrain_sample_field_device: the point count must be 0..2^26");
+    if (int rc = sample_field_check(c, opt, &o, "rt_terrain_sample_field_device")) return rc;
+    if (n > 0 && (!points_device || !results_device))
+        return fail(RT_ERR_INVALID, "rt_terrain_sample_field_device: null points or results");
+    if (int rc = check_texture(c->shader)) return rc;
+    if (int rc = host_flag_check(c->dev)) return rc;
+    if (n == 0) return RT_OK;
+    HIP_TRY(hipSetDevice(c->dev->ordinal));
+    return sample_field_enqueue(c, points_device, nullptr, (uint32_t)n, o, results_device, nullptr);
+}
+
+extern "C" int rt_terrain_sample_field(rt_compute c, const float* points, int n, const rt_field_options* opt,
+                                       float* results)
+{
+    rtq::FieldOptions o;
+    const char* why = "";
+    if (!c) return fail(RT_ERR_INVALID, "null compute");
+    if (int rc = rtq::check_count(n, &why)) return fail(rc, "rt_terrain_sample_field: the point count must be 0..2^26");
+    if (int rc = sample_field_check(c, opt, &o, "rt_terrain_sample_field")) return rc;
+    if (n > 0 && (!points || !results)) return fail(RT_ERR_INVALID, "rt_terrain_sample_field: null points or results");
+    if (int rc = check_texture(c->shader)) return rc;
+    if (int rc = host_flag_check(c->dev)) return rc;
+    if (n == 0) return RT_OK;
+    rt_device dev = c->dev;
+    HIP_TRY(hipSetDevice(dev->ordinal));
+    // one device block: the packed points, the results
+    const size_t np = (size_t)n, pts_b = np * 16, res_b = np * field_stride(o);
+    std::vector<float> packed(np * 4);
+    rtq::pack_points(points, n, packed.data());
+    char* d = nullptr;
+    HIP_TRY(hipMalloc(&d, pts_b + res_b));
+    auto run = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(d, packed.data(), pts_b, hipMemcpyHostToDevice, dev->stream));
+        if (int rc = sample_field_enqueue(c, d, nullptr, (uint32_t)n, o, d + pts_b, nullptr)) return rc;
+        HIP_TRY(hipMemcpyAsync(results, d + pts_b, res_b, hipMemcpyDeviceToHost, dev->stream));
+        HIP_TRY(hipStreamSynchronize(dev->stream));
+        return RT_OK;
+    };
+    const int rc = run();
+    if (rc) (void)hipStreamSynchronize(dev->stream); // whatever was queued is over before the block is freed
+    (void)hipFree(d);
+    return rc;
+}
+
+extern "C" int rt_terrain_sample_lattice_device(rt_compute c, const rt_lattice* lat, const rt_field_options* opt,
+                                                void* results_device, void* occupancy_device)
+{
+    rtq::FieldOptions o;
+    rtq::Lattice l;
+    uint32_t n = 0;
+    if (int rc = sample_lattice_check(c, lat, opt, &o, &l, &n, results_device, occupancy_device,
+                                      "rt_terrain_sample_lattice_device"))
+        return rc;
+    if (n == 0) return RT_OK;
+    HIP_TRY(hipSetDevice(c->dev->ordinal));
+    return sample_field_enqueue(c, nullptr, &l, n, o, results_device, occupancy_device);
+}
+
+extern "C" int rt_terrain_sample_lattice(rt_compute c, const rt_lattice* lat, const rt_field_options* opt, float* results,
+                                         uint32_t* occupancy)
+{
+    rtq::FieldOptions o;
+    rtq::Lattice l;
+    uint32_t n = 0;
+    if (int rc = sample_lattice_check(c, lat, opt, &o, &l, &n, results, occupancy, "rt_terrain_sample_lattice")) return rc;
+    if (n == 0) return RT_OK;
+    rt_device dev = c->dev;
+    HIP_TRY(hipSetDevice(dev->ordinal));
+    // one device block: the results, the occupancy words (both 16-byte aligned: res_b is a multiple of 4 only)
+    const size_t res_b = results ? ((size_t)n * field_stride(o) + 15) / 16 * 16 : 0;
+    const size_t occ_b = occupancy ? (size_t)((l.dims[0] + 31u) / 32u) * l.dims[1] * l.dims[2] * 4 : 0;
+    char* d = nullptr;
+    HIP_TRY(hipMalloc(&d, res_b + occ_b));
+    auto run = [&]() -> int {
+        if (int rc = sample_field_enqueue(c, nullptr, &l, n, o, results ? d : nullptr, occupancy ? d + res_b : nullptr)) return rc;
+        if (results) HIP_TRY(hipMemcpyAsync(results, d, (size_t)n * field_stride(o), hipMemcpyDeviceToHost, dev->stream));
+        if (occupancy) HIP_TRY(hipMemcpyAsync(occupancy, d + res_b, occ_b, hipMemcpyDeviceToHost, dev->stream));
+        HIP_TRY(hipStreamSynchronize(dev->stream));
+        return RT_OK;
+    };
+    const int rc = run();
+    if (rc) (void)hipStreamSynchronize(dev->stream); // whatever was queued is over before the block is freed
+    (void)hipFree(d);
+    return rc;
+}
+
+// ---------------------------------------------------------------------------
 // rt_readback_*: the asynchronous readback ring (struct rt_readback_s above; include/frosttrace.h)
 int rt_readback_create(rt_device d, int format, int depth, rt_readback* out)
 {

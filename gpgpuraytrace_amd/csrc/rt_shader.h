@@ -429,6 +429,38 @@ __device__ __forceinline__ float density_nomadplains(const Ctx& c, f3 p)
     return d + s;
 }
 
+// density_nomadplains' steep noise on its own, for a lattice column (k_fieldlattice): it reads p.x and p.z only, so
+// the points of one (x, z) column share it.  The same expression on the same inputs; the short cell path is chosen
+// by the noise's own two coordinates (either path gives the same bits, noise3d_z0).
+__device__ __forceinline__ float np_steep_noise(const Ctx& c, f3 p)
+{
+    const f3 p1 = rtm::scale(p, 0.4f);
+    const float a = p1.x * 0.007138f, b = p1.z * 0.007138f;
+    count_noise(c.nz);
+    const bool fast = !__ballot(!(rtm::max(rtm::abs(a), rtm::abs(b)) < kFastCellRange));
+    return fast ? noise3d_z0<true>(c.nz, a, b) : noise3d_z0<false>(c.nz, a, b);
+}
+
+// density_nomadplains with the steep noise given (sn = np_steep_noise of a point with this p.x and p.z): every
+// other operation as there, in its order, so the same bits.
+__device__ __forceinline__ float density_nomadplains_column(const Ctx& c, f3 p, float sn)
+{
+    float d = -p.y;
+    f3 p1 = rtm::scale(p, 0.4f);
+    float s = 0.0f;
+    f3 q0 = rtm::scale(p1, 0.006f);
+    const int n_oct = np_octaves(c, p);
+    const float qm = rtm::max(rtm::max(rtm::abs(q0.x), rtm::abs(q0.y)), rtm::abs(q0.z));
+    const bool fast = !__ballot(!(qm * c.nz.oct[n_oct].x < kFastCellRange));
+    s = fast ? np_fbm<true>(c, q0, n_oct) : np_fbm<false>(c, q0, n_oct);
+    s = rtm::pow_nonneg_wave(rtm::abs(fma(s, 30.0f, 1.0f)) * 35.0f, c.k->np_expo);
+    float steep = rtm::sat((sn - 0.2f) * 6.0f) * 7.5f;
+    s = terraces(s, p1.y, steep);
+    const float lb = rtm::sat((-p1.y + 10.0f) * 1.6f);
+    s = fma(__ballot(lb != 0.0f) ? rtm::pow_nonneg_wave(lb, 1.5f) : 0.0f, 19.0f, s);
+    return d + s;
+}
+
 #if RT_FBM_EXIT
 // (A/B build, rt_variants.h RT_FBM_EXIT) density_nomadplains with an exact early exit.  d = -y + F(s) + G
 // with F(s) = pow(|30 s + 1| 35, expo) and G (terraces + floor lift) independent of the FBM sum s.  After

@@ -184,6 +184,16 @@
 #define RT_FBM_EXIT 0
 #endif
 
+// A/B overrides of the field queries' lattice plan (rt_rayquery.h plan_field_lattice; scripts/field_query_bench.py):
+// RT_FIELD_ROWS > 0 replaces the plan's iy rows per strip, RT_FIELD_COLUMN 0 switches nomadplains' column reuse
+// off.  The results are the same bits either way.  profiles/r12/field_query.md.
+#ifndef RT_FIELD_ROWS
+#define RT_FIELD_ROWS 0
+#endif
+#ifndef RT_FIELD_COLUMN
+#define RT_FIELD_COLUMN 1
+#endif
+
 // ---- diagnostic builds (never in the product) ------------------------------------------------
 // RT_WAVE_TRACE          per-wave timeline of k_trace (make trace; scripts/wave_trace.py); fields 23-27: segment-job
 //                        time / jobs / loop steps, lane-refill long-ray loop steps / time

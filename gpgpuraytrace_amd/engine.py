@@ -756,6 +756,90 @@ class Terrain:
         return rc == _native.RT_OK
 
 
+    def sample_field(self, points, eye=None, normals=False, max_blocks=0):
+        """rt_terrain_sample_field: what the terrain IS at n points -- the density getDensity gives (> 0 inside),
+        and with normals getNormal (tracing.hlsl:107-116) there too, for every point, inside or outside.
+        points: (n, 3).  eye: the level-of-detail eye and getNormal's (default: the camera's, the compute's
+        current Eye).  Returns (n,) float32 densities, or with normals (n, 4) float32 rows normal xyz, density;
+        None if the call fails (lib().rt_last_error()).  max_blocks caps the grid.  Blocking; uses the camerarays
+        compute; needs set_camera() first."""
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        n = len(p)
+        opt = field_options(eye, normals, max_blocks)
+        self.update_shaders()
+        res = np.empty((n, 4) if normals else n, np.float32)
+        rc = lib().rt_terrain_sample_field(self.camera_compute._h, p.ctypes.data, n, C.byref(opt), res.ctypes.data)
+        return res if rc == _native.RT_OK else None
+
+    def sample_field_device(self, points_ptr, n, results_ptr, eye=None, normals=False, max_blocks=0):
+        """rt_terrain_sample_field_device: the same for device arrays -- points_ptr n x 4 float32 (pack_points'
+        layout: x y z _), results_ptr n float32 or with normals n x 4 float32, both 16-byte aligned -- enqueued on
+        the device's stream with no host synchronisation.  True on success."""
+        opt = field_options(eye, normals, max_blocks)
+        self.update_shaders()
+        rc = lib().rt_terrain_sample_field_device(self.camera_compute._h, points_ptr or None, int(n), C.byref(opt),
+                                                  results_ptr or None)
+        return rc == _native.RT_OK
+
+    def sample_lattice(self, origin, spacing, dims, eye=None, normals=False, occupancy=False, max_blocks=0):
+        """rt_terrain_sample_lattice: sample_field over the lattice of dims = (nx, ny, nz) points whose point
+        (ix, iy, iz) lies at fmaf(i, spacing, origin) per axis (one rounding), computed on the device: no
+        coordinates are uploaded.  Returns an array shaped (nz, ny, nx) float32, or (nz, ny, nx, 4) with normals
+        (normal xyz, density); with occupancy a tuple of it and the bit words (nz, ny, ceil(nx / 32)) uint32, bit
+        ix % 32 of word ix // 32 set where the density is > 0.  None if the call fails."""
+        lat, (nx, ny, nz) = lattice(origin, spacing, dims), (int(v) for v in dims)
+        opt = field_options(eye, normals, max_blocks)
+        self.update_shaders()
+        res = np.empty((nz, ny, nx, 4) if normals else (nz, ny, nx), np.float32)
+        occ = np.empty((nz, ny, (nx + 31) // 32), np.uint32) if occupancy else None
+        rc = lib().rt_terrain_sample_lattice(self.camera_compute._h, C.byref(lat), C.byref(opt), res.ctypes.data,
+                                             occ.ctypes.data if occupancy else None)
+        if rc != _native.RT_OK:
+            return None
+        return (res, occ) if occupancy else res
+
+    def sample_lattice_device(self, origin, spacing, dims, results_ptr=0, occupancy_ptr=0, eye=None, normals=False,
+                              max_blocks=0):
+        """rt_terrain_sample_lattice_device: the same into device arrays -- results_ptr nx ny nz float32 (x 4 with
+        normals, 16-byte aligned) or 0, occupancy_ptr ceil(nx / 32) ny nz uint32 or 0 (one of the two at least)
+        -- enqueued on the device's stream with no host synchronisation.  True on success."""
+        lat = lattice(origin, spacing, dims)
+        opt = field_options(eye, normals, max_blocks)
+        self.update_shaders()
+        rc = lib().rt_terrain_sample_lattice_device(self.camera_compute._h, C.byref(lat), C.byref(opt),
+                                                    results_ptr or None, occupancy_ptr or None)
+        return rc == _native.RT_OK
+
+
+def field_options(eye=None, normals=False, max_blocks=0):
+    """An rt_field_options block: the eye (None: the compute's Eye), RT_FIELD_NORMAL, the grid's cap."""
+    opt = _native.RtFieldOptions()
+    opt.size = C.sizeof(_native.RtFieldOptions)
+    opt.flags = _native.RT_FIELD_NORMAL if normals else 0
+    if eye is not None:
+        opt.flags |= _native.RT_RAYS_EYE
+        opt.eye[:] = [float(x) for x in np.asarray(eye, np.float32).reshape(3)]
+    opt.max_blocks = int(max_blocks)
+    return opt
+
+
+def lattice(origin, spacing, dims):
+    """An rt_lattice block: origin and spacing (3 floats each), dims (nx, ny, nz)."""
+    lat = _native.RtLattice()
+    lat.origin[:] = [float(x) for x in np.asarray(origin, np.float32).reshape(3)]
+    lat.spacing[:] = [float(x) for x in np.asarray(spacing, np.float32).reshape(3)]
+    lat.dims[:] = [int(x) for x in dims]
+    return lat
+
+
+def pack_points(points):
+    """The field queries' device layout: (n, 4) float32 rows x y z 0 (one 16-byte load per point)."""
+    p = np.asarray(points, np.float32).reshape(-1, 3)
+    out = np.zeros((len(p), 4), np.float32)
+    out[:, 0:3] = p
+    return out
+
+
 RAY_MODES ={"auto": 0, "segments": _native.RT_RAYS_FORCE_SEGMENTS, "lanes": _native.RT_RAYS_FORCE_LANES}
 
 

@@ -548,6 +548,67 @@ int rt_terrain_shade_rays(rt_compute screen_cs, const float* origins, const floa
 int rt_terrain_shade_rays_device(rt_compute screen_cs, const void* rays_device, int n, const rt_surface_options* opt,
                                  void* results_device, void* rgba8_device, void* steps_device);
 
+/* ---- field queries (ABI 9, additive; no reference counterpart) ----
+ * What the terrain IS at a place, without a ray: the density field itself (getDensity, > 0 inside) and its normal.
+ * Voxel and occupancy grids for collision and path finding, density volumes for mesh export or a slice through the
+ * world, inside/outside tests for spawn points and buoyancy.  For point p and one eye E per call:
+ *     d        = getDensity(p)                                                    (terrain.hlsl of the landscape)
+ *     result_i = d                                                                one float a point
+ *   with RT_FIELD_NORMAL:
+ *     n        = getNormal(float4(p, d))                                          (tracing.hlsl:107-116)
+ *     result_i = float4(n, d)                                                     16-byte aligned in the device forms
+ *   E     replaces Eye in getDensity (nomadplains' octave count) and in getNormal's eps = 0.005 |p - E|.  Without
+ *         RT_RAYS_EYE it is the compute's current Eye variable.  One per call.
+ *   The normal is computed for EVERY point, inside or outside (the gradient direction of the field, as the shaders
+ *         take it: one-sided differences over eps).  Where all three differences are zero (p == E is one case) the
+ *         normal is unspecified.  Non-finite points give unspecified results.
+ * A lattice (rt_lattice) is dims[0] x dims[1] x dims[2] = nx x ny x nz points computed on the device: point
+ *   (ix, iy, iz) has the coordinate fmaf((float)i, spacing, origin) on each axis (ONE rounding) and the result index
+ *   (iz * ny + iy) * nx + ix.  Its results are bit for bit the point form's for the same coordinates.  A spacing may
+ *   be negative or zero.
+ *   occupancy (optional) is one bit per lattice point, d > 0 (the hit test of tracescreen.hlsl:29), packed in
+ *   uint32 words: ceil(nx / 32) words per (iy, iz) row, word index (iz * ny + iy) * ceil(nx / 32) + ix / 32, bit
+ *   ix % 32; the padding bits of a row's last word are 0.  At least one of results and occupancy must be given;
+ *   occupancy alone computes no normal.
+ * rt_field_options (opt may be NULL: all defaults): size = sizeof(rt_field_options) of the caller's header (later
+ *   versions append fields); flags: RT_RAYS_EYE (as above) and RT_FIELD_NORMAL, every other bit is an error;
+ *   max_blocks caps the grid (0: every CU less rt_device_reserve_cus).
+ * rt_terrain_sample_field: host arrays (points: 3n floats x y z; results: n floats, or 4n with RT_FIELD_NORMAL);
+ *   blocking.
+ * rt_terrain_sample_field_device: device arrays (points n x 4 floats x y z _, 16-byte aligned, the spare word
+ *   ignored; results n floats, or n x 4 floats 16-byte aligned), enqueued on the compute's device stream with no
+ *   host synchronisation: order other streams with rt_device_wait_event / rt_device_record_event.
+ * rt_terrain_sample_lattice / _device: the same two forms for a lattice (results nx ny nz floats, or x 4; occupancy
+ *   ceil(nx / 32) ny nz uint32); no coordinates are uploaded or read.
+ * All: n == 0 or a dims product of 0 is RT_OK and launches nothing.  RT_ERR_INVALID: n < 0, n or nx ny nz above
+ *   2^26, a dim above 4096, a non-finite origin or spacing, a NULL compute, lattice or required array, results and
+ *   occupancy both NULL, opt->size below the first version (24), unknown flags.  RT_ERR_STATE without texPerm2D
+ *   bound, or with the fail-safe word set.  Either kind of compute.  A query reads no frame state and changes none:
+ *   it flushes no deferred frame, invalidates no ahead / fused prepass or captured graph, and uploads the constants
+ *   it needs to a copy of its own, so it may run between any two renders.
+ * Out of scope: mesh extraction (marching cubes over the volume is the caller's); the fog field (getFog); an eye
+ *   per point; a caller-chosen eps for the normal; finite differences between lattice neighbours (the normal is
+ *   getNormal's, three more density samples a point). */
+enum { RT_FIELD_NORMAL = 32 };
+typedef struct {
+    uint32_t size;
+    uint32_t flags;
+    float eye[3];
+    uint32_t max_blocks;
+} rt_field_options;
+typedef struct {
+    float origin[3];
+    float spacing[3];
+    uint32_t dims[3]; /* nx, ny, nz */
+} rt_lattice;
+int rt_terrain_sample_field(rt_compute cs, const float* points, int n, const rt_field_options* opt, float* results);
+int rt_terrain_sample_field_device(rt_compute cs, const void* points_device, int n, const rt_field_options* opt,
+                                   void* results_device);
+int rt_terrain_sample_lattice(rt_compute cs, const rt_lattice* lat, const rt_field_options* opt, float* results,
+                              uint32_t* occupancy);
+int rt_terrain_sample_lattice_device(rt_compute cs, const rt_lattice* lat, const rt_field_options* opt,
+                                     void* results_device, void* occupancy_device);
+
 /* ---- diagnostics (primitive-level parity tests; no reference counterpart) ----
  * rt_debug_math: device evaluation of the numeric primitives of DESIGN.md §Numerics
  *   (op 0 exp2, 1 log2, 2 exp, 3 sin, 4 cos, 5 sqrt, 6 rcp, 7 rsqrt, 8 pow, 9 max,
