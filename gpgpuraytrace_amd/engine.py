@@ -840,7 +840,7 @@ def pack_points(points):
     return out
 
 
-RAY_MODES ={"auto": 0, "segments": _native.RT_RAYS_FORCE_SEGMENTS, "lanes": _native.RT_RAYS_FORCE_LANES}
+RAY_MODES = {"auto": 0, "segments": _native.RT_RAYS_FORCE_SEGMENTS, "lanes": _native.RT_RAYS_FORCE_LANES}
 
 
 def ray_options(eye=None, mode="auto", max_blocks=0):

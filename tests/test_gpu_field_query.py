@@ -285,7 +285,8 @@ def test_arguments():
     from gpgpuraytrace_amd import _native
     L = G.lib()
     p = _points("nomadplains")[:8].copy()
-    res = np.zeros((8, 4), np.float32)
+    # room for the largest host result below: the 16 points of `good` with their normals (256 bytes)
+    res = np.zeros((16, 4), np.float32)
     dev, ter = _make()
     cs = ter.camera_compute._h
     pp, rp = p.ctypes.data, res.ctypes.data
