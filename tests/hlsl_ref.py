@@ -1,7 +1,7 @@
 """Float64 numpy restatement of the terrain shaders (TEST INFRASTRUCTURE, an independent checker).
 
 Follows the HLSL line by line in double precision, as tests/sky_ref.py does for the sky:
-    Media/common/shaders/tracing.hlsl:107-116 (getNormal), :124-134 (getPixelRay)
+    Media/common/shaders/tracing.hlsl:32-105 (traceRay), :107-116 (getNormal), :124-134 (getPixelRay)
     Media/common/shaders/tracescreen.hlsl:16-48 (the hit and the miss composite of traceSample)
     Media/{nomadplains,simple,testing,greenrocks}/shaders/terrain.hlsl (getDensity, getFog)
     Media/{nomadplains,simple,testing,greenrocks}/shaders/color.hlsl (getColor)
@@ -10,11 +10,14 @@ widened to float64; everything else is real-number arithmetic (numpy `**`, log2,
 code, no fma rule and no polynomial with oracle/rt_oracle.c or rt_shader.h, so agreement within a tolerance pins
 their arithmetic to the HLSL's real-number meaning (tests/test_hlsl_kat.py, tests/test_gpu_hlsl_kat.py).
 
-Not restated: the march (traceRay), whose outcome is an input wherever a stage needs it (the shadow ray of
-getColor: whether it hit and its fcolord.w; traceSample's rr); the AA patterns, AO and the camera matrices.
-RECORDING changes only march constants.  Dead code of the HLSL whose value never reaches a result is left out
-where it costs noise evaluations (getColor's blend, n1 and first FBM, color2, `s *= 30`, the `precision` of the
-shadow ray, which is a march input); cheap dead terms are evaluated so that their literals stay in the table.
+The march (traceRay, tracing.hlsl:32-105) is restated teacher-forced (march(), at the end of this module): its
+branches and densities are read from the implementation under test, its own arithmetic is float64
+(tests/test_march_kat.py, tests/test_gpu_march_kat.py).  No stage marches by itself: the march's outcome is an
+input wherever one needs it (the shadow ray of getColor: whether it hit and its fcolord.w; traceSample's rr).
+Not restated: the AA resolve, AO and the camera matrices.  RECORDING changes only march constants.  Dead code of
+the HLSL whose value never reaches a result is left out where it costs noise evaluations (getColor's blend, n1 and
+first FBM, color2, `s *= 30`; the `precision` of the shadow ray is a march input, restated by shadow_ray()); cheap
+dead terms are evaluated so that their literals stay in the table.
 
 Loops bounded by a float `detail` (nomadplains' getDensity, simple's getColor) are the one discontinuity besides
 the march: density, normal, color and sample_color return an `unsafe` mask next to the value, set where
@@ -23,8 +26,9 @@ those points out.
 
 Every literal of getDensity, getFog and getColor has a name in LITERALS (its text as the HLSL prints it, and where
 it stands); `tweak={name: value}` replaces it, which is how the mutation check of test_hlsl_kat.py shows that the
-bounds notice a misread constant.  Two tweaks are not numbers: "<land>.color.swizzle" ("yxz" by default) names the
-coordinates of p that the colour FBM's three factors multiply.
+bounds notice a misread constant; the march's literals ("march.*") and the shadow ray's ("<land>.shadow.*") stand
+in the same table.  Some tweaks are not numbers: "march.structure" names one of MARCH_STRUCTURES, and
+"<land>.color.swizzle" ("yxz" by default) names the coordinates of p that the colour FBM's three factors multiply.
 """
 import os
 
@@ -159,13 +163,14 @@ def mutants(prefix):
                 yield name + "+1", {name: f32(text) + 1.0}
     if prefix + ".swizzle" in SWIZZLES:
         yield prefix + ".swizzle", {prefix + ".swizzle": "yzx"}
+    yield from _march_mutants(prefix)
 
 
 class _K:
     def __init__(self, prefix, tweak):
         self.prefix, self.tweak = prefix, tweak or {}
         for k in self.tweak:
-            assert k in LITERALS or k in SWIZZLES, k
+            assert k in LITERALS or k in SWIZZLES or k in STRUCTURES, k
 
     def __call__(self, name):
         full = self.prefix + "." + name
@@ -422,3 +427,153 @@ def pixel_ray(consts, px, py):
 def unorm8(x):
     """The RGBA8 code of a colour: saturate, then round(x * 255) (round half up; the tests allow one code)."""
     return np.floor(_sat(np.asarray(x, np.float64)) * 255.0 + 0.5).astype(np.int64)
+
+
+# ------------------------------------------------------------------------------------------------
+# The march (traceRay, Media/common/shaders/tracing.hlsl:32-105), teacher-forced.
+_T = "common/shaders/tracing.hlsl"
+_lits("march", _T + ":32", ray_step="0.03")
+_lits("march", _T + ":33", final_precision="0.02")
+_lits("march", _T + ":36", recording_density_factor="0.15")
+_lits("march", _T + ":37", recording_step_factor="1.001")
+_lits("march", _T + ":39", density_factor="0.35")
+_lits("march", _T + ":40", step_factor="1.009")
+_lits("march", _T + ":54", first_one="1.0")
+_lits("march", _T + ":61", mid_half="0.5")
+_lits("march", _T + ":86", refine="0.3")
+_lits("march", _T + ":90", stepmult_one="1.0", density_bias="5.0", stepmult_cap="0.0")
+# the shadow ray of getColor, which every landscape's color.hlsl casts with the same constants
+for _land, _l0 in (("nomadplains", 47), ("testing", 19), ("simple", 49), ("greenrocks", 18)):
+    _T = "%s/shaders/color.hlsl" % _land
+    _lits(_land + ".shadow", _T + ":%d" % _l0, mip_half="0.5", mip_floor="0")
+    _lits(_land + ".shadow", _T + ":%d" % (_l0 + 3), mip_bias="3.2", mip_gain="3.0", precision_floor="1.0",
+          precision_gain="8.0")
+    _lits(_land + ".shadow", _T + ":%d" % (_l0 + 4), start="0.4", length="100.0")
+
+# what only the RECORDING build reads, and what only the other reads
+MARCH_RECORDING = ("march.recording_density_factor", "march.recording_step_factor")
+MARCH_NOT_RECORDING = ("march.density_factor", "march.step_factor")
+# structural misreadings of the loop: values of the tweak "march.structure"
+MARCH_STRUCTURES = {
+    "dist_minus_step": "a hit backs up by step, not lastStep (:85)",
+    "laststep_before_growth": "lastStep from step before `step *= RAY_STEP_FACTOR` (:92-93)",
+    "no_fog_refund": "no `f -= fogstep` on a hit (:88)",
+    "fog_by_laststep": "fogstep weighted by lastStep, not step (:78)",
+    "dir_not_normalised": "rayp from dir as given, without `dir /= dirLength` (:56, :71)",
+    "no_dirlength_in_first_step": "the first step without dirLength (:54)",
+}
+MARCH_FOG = ("march.mid_half", "march.structure=no_fog_refund", "march.structure=fog_by_laststep")
+TIE_BAND = 1e-5
+STRUCTURES = ("march.structure",)
+
+
+def _march_mutants(prefix):
+    if prefix == "march":
+        for s in MARCH_STRUCTURES:
+            yield "march.structure=" + s, {"march.structure": s}
+
+
+def shadow_ray(land, dist, tweak=None):
+    """The arguments of getColor's shadow ray (nomadplains color.hlsl:47-51 and its twins): (dist0, enddist,
+    stepmod (n,)) of traceRay(p, 0.4f, SHADOW_LENGTH, precision, SunDirection, true, true) for a hit at `dist`."""
+    K = _K(land + ".shadow", tweak)
+    dist = np.asarray(dist, np.float64).reshape(-1)
+    mipf = np.maximum(K("mip_half") * np.log2(dist), K("mip_floor"))
+    precision = np.maximum((mipf - K("mip_bias")) * K("mip_gain"), K("precision_floor")) * K("precision_gain")
+    return K("start"), K("length"), precision
+
+
+class March:
+    """What march() returns; K steps, n rays.  Index k of the (K + 1, n) arrays is the state after k steps (0: at
+    loop entry); index k - 1 of the (K, n) arrays is step k."""
+
+
+def march(land, p, dir, dist0, enddist, stepmod, recording, calcfog, skiprefine, d, rayp, dist, ran, tweak=None,
+          tab=None):
+    """traceRay (tracing.hlsl:47-105) with its branches and densities read from an implementation's own trajectory.
+
+    p, dir (n, 3); dist0, enddist, stepmod scalars or (n,); recording, calcfog, skiprefine the build's and the call's
+    flags.  Observed, step k at index k - 1: d (K, n) the density of the k-th sample, rayp (K, n, 3) its position,
+    dist (K, n) the distance after the k-th update, ran (K, n) whether the ray ran a k-th step (rows that did not
+    are not read, and their state stays as it was).  The branch of step k is d[k] > 0 and stepmult reads d[k]; the
+    step, lastStep and f run free in float64 from line 54 on; each distance is advanced once from the observed one
+    before it.  Nothing here knows of a cap on the step count.
+
+    Returns a March with pos (K, n, 3) the predicted sample p + normalize(dir) * dist[k-1], dist (K, n) the
+    predicted distance after step k, step and last_step (K + 1, n), f (K + 1, n, 4) the accumulated fog (zero
+    without calcfog), cond (K + 1, n) the loop condition `dist < enddist && step > RAY_MIN_LIMIT` at the observed
+    distance and the restated step, ended (K + 1, n) where skiprefine's break has ended the ray, and unsafe
+    (K + 1, n) where the condition lies within TIE_BAND (relative) of a tie."""
+    C = _K("march", tweak)
+    structure = C.tweak.get("march.structure")
+    assert structure is None or structure in MARCH_STRUCTURES, structure
+    p, dir = _vec(p), _vec(dir)
+    n = len(p)
+    d = np.asarray(d, np.float64)
+    steps = d.shape[0]
+    rayp_obs, dist_obs, ran = np.asarray(rayp, np.float64), np.asarray(dist, np.float64), np.asarray(ran, bool)
+    assert d.shape == dist_obs.shape == ran.shape == (steps, n) and rayp_obs.shape == (steps, n, 3)
+    dist0, enddist, stepmod = (np.broadcast_to(np.asarray(v, np.float32).astype(np.float64).reshape(-1), (n,))
+                               for v in (dist0, enddist, stepmod))
+    ray_step = C("ray_step")  # :32
+    min_limit = C("final_precision") * ray_step  # :33-34
+    density_factor = C("recording_density_factor") if recording else C("density_factor")  # :35-41
+    step_factor = C("recording_step_factor") if recording else C("step_factor")
+
+    dir_length = np.linalg.norm(dir, axis=1)  # :53
+    first = ray_step * stepmod * (1.0 if structure == "no_dirlength_in_first_step" else dir_length)
+    step = first - dist0 * (C("first_one") - step_factor)  # :54
+    last_step = step.copy()  # :55
+    ndir = dir if structure == "dir_not_normalised" else dir / dir_length[:, None]  # :56
+    f = np.zeros((n, 4))  # :50
+    if calcfog:  # :59-63
+        half = C("mid_half")
+        f = f + fog(land, p + ndir * (dist0 * half)[:, None], dist0 * half, None, tab) * dist0[:, None]
+
+    out = March()
+    out.pos, out.dist = np.zeros((steps, n, 3)), np.zeros((steps, n))
+    out.step, out.last_step = np.zeros((steps + 1, n)), np.zeros((steps + 1, n))
+    out.f = np.zeros((steps + 1, n, 4))
+    out.cond, out.unsafe, out.ended = (np.zeros((steps + 1, n), bool) for _ in range(3))
+    ended = np.zeros(n, bool)
+
+    def record(k, at):
+        out.step[k], out.last_step[k], out.f[k], out.ended[k] = step, last_step, f, ended
+        out.cond[k] = (at < enddist) & (step > min_limit)  # :68
+        out.unsafe[k] = ((np.abs(at - enddist) <= TIE_BAND * np.maximum(1.0, np.abs(enddist)))
+                         | (np.abs(step - min_limit) <= TIE_BAND * min_limit))
+
+    at = dist0.copy()
+    record(0, at)
+    for k in range(steps):
+        r = ran[k]
+        out.pos[k] = p + ndir * at[:, None]  # :71
+        dk = d[k]
+        hit = r & (dk > 0.0)  # :81, observed
+        air = r & ~hit
+        fogstep = np.zeros((n, 4))
+        if calcfog and r.any():  # :76-79
+            rows = np.flatnonzero(r)
+            weight = last_step if structure == "fog_by_laststep" else step
+            fogstep[rows] = fog(land, rayp_obs[k][rows], at[rows], None, tab) * weight[rows, None]
+        nxt = at.copy()
+        step, last_step, f = step.copy(), last_step.copy(), f.copy()
+        if skiprefine:  # :83
+            ended = ended | hit
+        else:
+            back = step if structure == "dist_minus_step" else last_step
+            nxt[hit] = at[hit] - back[hit]  # :85
+            step[hit] = step[hit] * C("refine")  # :86
+            if structure != "no_fog_refund":
+                f[hit] = f[hit] - fogstep[hit]  # :88
+        stepmult = C("stepmult_one") + np.abs(np.minimum(dk + C("density_bias"), C("stepmult_cap"))) ** density_factor  # :90
+        before = step[air]
+        step[air] = step[air] * step_factor  # :92
+        last_step[air] = (before if structure == "laststep_before_growth" else step[air]) * stepmult[air]  # :93
+        nxt[air] = at[air] + last_step[air]  # :94
+        f[air] = f[air] + fogstep[air]  # :95
+        out.dist[k] = nxt
+        # the next step starts from the observed distance, not from the prediction
+        at = np.where(r, dist_obs[k], at)
+        record(k + 1, at)
+    return out

@@ -1,6 +1,7 @@
 """The oracle's shading stages at inputs of the caller's own (TEST INFRASTRUCTURE): builds, binds and caches
 tests/tools/stage_ref.c, which includes the oracle's source and exports its static get_normal, get_fog,
-get_pixel_ray and get_color.  Built with the oracle's own flags into tests/tools/_build/."""
+get_pixel_ray, get_color and trace_ray, and its AA offset tables.  Built with the oracle's own flags into
+tests/tools/_build/."""
 import ctypes as C
 import os
 import subprocess
@@ -34,8 +35,14 @@ def lib():
         L.st_fog.argtypes = [nzp, frp, fp, fp, C.c_int64, fp]
         L.st_pixel_ray.argtypes = [nzp, frp, fp, C.c_int64, fp, fp]
         L.st_color.argtypes = [nzp, frp, fp, fp, fp, fp, C.c_int64, fp, C.c_void_p, fp]
-        for f in (L.st_normal, L.st_fog, L.st_pixel_ray, L.st_color):
+        L.st_trace_ray.argtypes = [nzp, frp, fp, fp, fp, fp, fp, C.c_int64, C.c_int, C.c_int, C.c_int, fp, fp, fp,
+                                   C.c_void_p]
+        for f in (L.st_normal, L.st_fog, L.st_pixel_ray, L.st_color, L.st_trace_ray):
             f.restype = None
+        L.st_shadow_precision.argtypes = [fp, C.c_int64, fp]
+        L.st_shadow_precision.restype = None
+        L.st_aa_offsets.argtypes = [C.c_int, fp]
+        L.st_aa_offsets.restype = C.c_int
         _lib = L
     return _lib
 
@@ -84,3 +91,36 @@ def color(land, p, n, d, dist, eye, sun=SH.SUN):
     lib().st_color(C.byref(O.noise_tables()), C.byref(fr), O._fp(p), O._fp(n), O._fp(d), O._fp(dist), len(p), O._fp(rgb),
                    cls.ctypes.data, O._fp(w))
     return rgb, cls, w
+
+
+def trace_ray(land, p, dist, enddist, stepmod, dir, eye, calcfog, skiprefine, max_steps=0, recording=0, sun=SH.SUN):
+    """The oracle's trace_ray (tracing.hlsl:47-105) with every argument the caller's: p, dir (n, 3); dist, enddist,
+    stepmod scalars or (n,); max_steps the build's cap (0: none).  (pd (n, 4), fcolord (n, 4), density (n,) float32,
+    steps (n,) uint32)."""
+    p, dir = _a(p, 3), _a(dir, 3)
+    n = len(p)
+    assert len(dir) == n
+    dist, enddist, stepmod = (np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float32).reshape(-1), (n,)))
+                              for v in (dist, enddist, stepmod))
+    pd, fc = np.zeros((n, 4), np.float32), np.zeros((n, 4), np.float32)
+    dens, steps = np.zeros(n, np.float32), np.zeros(n, np.uint32)
+    fr = SH.frame(eye, land, sun, recording)
+    lib().st_trace_ray(C.byref(O.noise_tables()), C.byref(fr), O._fp(p), O._fp(dist), O._fp(enddist), O._fp(stepmod),
+                       O._fp(dir), n, int(bool(calcfog)), int(bool(skiprefine)), int(max_steps), O._fp(pd), O._fp(fc),
+                       O._fp(dens), steps.ctypes.data)
+    return pd, fc, dens, steps
+
+
+def aa_offsets(samples):
+    """getSampleOffset(0 .. samples-1) as the oracle's tracescreen selects and scales them: (samples, 2) float32."""
+    out = np.zeros((16, 2), np.float32)
+    n = lib().st_aa_offsets(int(samples), O._fp(out))
+    return out[:n].copy()
+
+
+def shadow_precision(dist):
+    """The stepmod get_color gives its shadow ray for a hit at dist (color.hlsl:47-50): (n,) float32."""
+    dist = np.ascontiguousarray(dist, np.float32).reshape(-1)
+    out = np.zeros(len(dist), np.float32)
+    lib().st_shadow_precision(O._fp(dist), len(dist), O._fp(out))
+    return out

@@ -63,7 +63,10 @@ MEASURED = {
 def bound(stage, land=None):
     """Twice the measured worst, rounded up to one significant digit."""
     m = MEASURED[stage]
-    m = m if land is None else m[LANDS.index(land)]
+    return twice_rounded_up(m if land is None else m[LANDS.index(land)])
+
+
+def twice_rounded_up(m):
     x = 2.0 * m
     if x == 0.0:
         return 0.0

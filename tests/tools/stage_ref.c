@@ -2,7 +2,8 @@
  * stage_ref.c -- TEST INFRASTRUCTURE: the oracle's shading stages at inputs of the caller's own, for the
  * known-answer tests against the float64 restatement of the HLSL (tests/hlsl_ref.py, tests/test_hlsl_kat.py).
  * The oracle keeps get_normal (tracing.hlsl:107-116), get_fog (terrain.hlsl), get_pixel_ray (tracing.hlsl:124-134)
- * and get_color (color.hlsl) static, so this includes its source and calls them per element.  Built by
+ * and get_color (color.hlsl) static, so this includes its source and calls them per element; likewise trace_ray
+ * (tracing.hlsl:47-105) and the AA offset tables (antialiasing.hlsl:9-59) for tests/test_march_kat.py.  Built by
  * tests/stage_ref.py with the oracle's own flags.
  *
  * fr->eye is Eye, fr->sun SunDirection, fr->landscape, fr->recording, fr->width, fr->height, fr->projection and
@@ -46,6 +47,47 @@ void st_pixel_ray(const ro_noise* nz, const ro_frame* fr, const float* pixel, in
         outp[3 * i] = p.x; outp[3 * i + 1] = p.y; outp[3 * i + 2] = p.z;
         outdir[3 * i] = d.x; outdir[3 * i + 1] = d.y; outdir[3 * i + 2] = d.z;
     }
+}
+
+/* traceRay (tracing.hlsl:47-105) with every argument the caller's own, for the march's known-answer tests
+ * (tests/test_march_kat.py): p, dir 3 floats a ray; dist, enddist, stepmod 1 each; calcfog, skiprefine and the
+ * build's max_steps (0: none) per call; fr->recording picks the constants.  pd, fcolord: 4 floats a ray. */
+void st_trace_ray(const ro_noise* nz, const ro_frame* fr, const float* p, const float* dist, const float* enddist,
+                  const float* stepmod, const float* dir, int64_t n, int calcfog, int skiprefine, int max_steps,
+                  float* pd, float* fcolord, float* density, uint32_t* steps)
+{
+#pragma omp parallel for schedule(dynamic, 16)
+    for (int64_t i = 0; i < n; ++i) {
+        ctx c;
+        ctx_init(&c, nz, fr);
+        ray_result rr = trace_ray(&c, v3(p[3 * i], p[3 * i + 1], p[3 * i + 2]), dist[i], enddist[i], stepmod[i],
+                                  v3(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]), calcfog, skiprefine, max_steps);
+        pd[4 * i] = rr.pd.x; pd[4 * i + 1] = rr.pd.y; pd[4 * i + 2] = rr.pd.z; pd[4 * i + 3] = rr.pd.w;
+        fcolord[4 * i] = rr.fcolord.x; fcolord[4 * i + 1] = rr.fcolord.y;
+        fcolord[4 * i + 2] = rr.fcolord.z; fcolord[4 * i + 3] = rr.fcolord.w;
+        density[i] = rr.density;
+        steps[i] = (uint32_t)rr.steps;
+    }
+}
+
+/* the stepmod of getColor's shadow ray (color.hlsl:47-50) for hits at dist */
+void st_shadow_precision(const float* dist, int64_t n, float* out)
+{
+    for (int64_t i = 0; i < n; ++i) out[i] = shadow_precision(dist[i]);
+}
+
+/* getSampleOffset(num) for AA_SAMPLES = samples (antialiasing.hlsl:9-59): the table ro_tracescreen selects, by its
+ * own selector and its own division by 16.  out: 2 floats a sample; returns the sample count. */
+int st_aa_offsets(int samples, float* out)
+{
+    int aa = samples;
+    if (aa != 2 && aa != 4 && aa != 8 && aa != 16) aa = 1;
+    const float (*offs)[2] = aa_table(aa);
+    for (int a = 0; a < aa; ++a) {
+        out[2 * a] = offs[a][0] * (1.0f / 16.0f);
+        out[2 * a + 1] = offs[a][1] * (1.0f / 16.0f);
+    }
+    return aa;
 }
 
 /* getColor(p, nrm, d, dist): p, nrm, d 3 floats each, dist 1; rgb: 3.  classes: 1 where the shadow ray ended in
