@@ -144,11 +144,18 @@ struct RtRayQuery {
 };
 bool rt_launch_rayquery(const RtLaunch& a, const RtRayQuery& q);
 
+// The march of a surface or shaded query's rays: t_min, t_max, stepmod and max_steps (0: unbounded) hold for every
+// ray; with ray_range the rays' spare words are t_min_i and t_max_i instead.
+struct RtMarchParams {
+    float t_min, t_max, stepmod;
+    int max_steps;
+    bool ray_range;
+};
+
 // A surface query (rt_terrain_trace_surface): the refined march tracescreen runs for its pixels
 // (traceRay with skiprefine off, tracing.hlsl:47-105) and getNormal (:107-116) for the same packed rays ->
-// results[2n] (pd.xyz, pd.w | normal, density; the normal 0 where density <= 0) and, if set, steps[n].  t_min,
-// t_max, stepmod and max_steps (0: unbounded) hold for every ray; with ray_range the rays' spare words are
-// t_min_i and t_max_i instead.  Shapes, grid and counter as RtRayQuery's.
+// results[2n] (pd.xyz, pd.w | normal, density; the normal 0 where density <= 0) and, if set, steps[n].  Shapes,
+// grid and counter as RtRayQuery's.
 struct RtSurfQuery {
     const float4* rays;
     float4* results;
@@ -158,9 +165,7 @@ struct RtSurfQuery {
     int bs, lpr;
     uint32_t blocks;
     uint32_t* counter;
-    float t_min, t_max, stepmod;
-    int max_steps;
-    bool ray_range;
+    RtMarchParams march;
 };
 bool rt_launch_surfquery(const RtLaunch& a, const RtSurfQuery& q);
 
@@ -177,9 +182,7 @@ struct RtShadeQuery {
     float eye[3];
     uint32_t blocks;
     uint32_t* counter;
-    float t_min, t_max, stepmod;
-    int max_steps;
-    bool ray_range;
+    RtMarchParams march;
 };
 bool rt_launch_shadequery(const RtLaunch& a, const RtShadeQuery& q);
 

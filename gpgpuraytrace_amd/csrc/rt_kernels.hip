@@ -2497,6 +2497,48 @@ void rt_launch_shard_copy(hipStream_t s, const ShardJobs& jobs, int n, int w, in
 }
 
 // ---------------------------------------------------------------------------
+// The queries' launch dispatch (host side): a launch's run-time choices as its kernel's template arguments.
+namespace {
+
+template <int V>
+using Int = std::integral_constant<int, V>;
+
+// f(Int<L>) with the launch's landscape
+template <class F>
+void with_landscape(const RtLaunch& a, F f)
+{
+    switch (a.landscape) {
+    case RT_TESTING: f(Int<RT_TESTING>{}); break;
+    case RT_SIMPLE: f(Int<RT_SIMPLE>{}); break;
+    case RT_GREENROCKS: f(Int<RT_GREENROCKS>{}); break;
+    default: f(Int<RT_NOMADPLAINS>{}); break;
+    }
+}
+
+// f(std::true_type) or f(std::false_type)
+template <class F>
+void with_bool(bool b, F f)
+{
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+// f(Int<BS>, Int<LPR>) with a segment shape's (block size, lanes per ray), one of the pairs of the prepass's
+// ladder; false: no such pair (f not called)
+template <class F>
+bool with_segment(int bs, int lpr, F f)
+{
+    if (bs == RT_PREPASS_BS1 && lpr == RT_PREPASS_LPR1) f(Int<RT_PREPASS_BS1>{}, Int<RT_PREPASS_LPR1>{});
+    else if (bs == 512 && lpr == 32) f(Int<512>{}, Int<32>{});
+    else if (bs == 512 && lpr == 8) f(Int<512>{}, Int<8>{});
+    else if (bs == 512 && lpr == 4) f(Int<512>{}, Int<4>{});
+    else return false;
+    return true;
+}
+
+} // namespace
+
+// ---------------------------------------------------------------------------
 // Ray queries (rt_terrain_trace_rays): camerarays.hlsl:12-21 for rays read from memory instead of
 // getPixelRay's.  Ray i is two 16-byte loads (ox oy oz _ | dx dy dz _), its result one 16-byte store
 // (+ the loop's iteration count with STEPS).  The LOD eye (nomadplains' octave count reads it) is a
@@ -2622,50 +2664,31 @@ __global__ void __launch_bounds__(1024) k_rayquery(const RtConsts* __restrict__ 
 #endif
 }
 
-template <int L>
-void launch_rayquery_lanes(const RtLaunch& a, const RtRayQuery& q)
-{
-    // the live-lane count at or below which a wave refills (RT_RAYQ_REFILL; at most 63, so a refill claims >= 1 ray)
-    constexpr uint32_t thr = RT_RAYQ_REFILL < 63 ? RT_RAYQ_REFILL : 63;
-    if (q.steps)
-        hipLaunchKernelGGL((k_rayquery<L, true>), dim3(q.blocks), dim3(1024), 0, a.stream, a.consts, a.perm2d, a.grad,
-                           q.rays, q.results, q.steps, q.n, q.eye[0], q.eye[1], q.eye[2], q.counter, thr);
-    else
-        hipLaunchKernelGGL((k_rayquery<L, false>), dim3(q.blocks), dim3(1024), 0, a.stream, a.consts, a.perm2d, a.grad,
-                           q.rays, q.results, q.steps, q.n, q.eye[0], q.eye[1], q.eye[2], q.counter, thr);
-}
-
-template <int BS, int LPR>
-void launch_rayquery_seg(const RtLaunch& a, const RtRayQuery& q)
-{
-    if (q.steps)
-        hipLaunchKernelGGL((k_rayquery_seg<true, BS, LPR>), dim3(q.blocks), dim3(BS), 0, a.stream, a.consts, a.perm2d,
-                           a.grad, q.rays, q.results, q.steps, q.n, q.eye[0], q.eye[1], q.eye[2]);
-    else
-        hipLaunchKernelGGL((k_rayquery_seg<false, BS, LPR>), dim3(q.blocks), dim3(BS), 0, a.stream, a.consts, a.perm2d,
-                           a.grad, q.rays, q.results, q.steps, q.n, q.eye[0], q.eye[1], q.eye[2]);
-}
-
 } // namespace
 
 bool rt_launch_rayquery(const RtLaunch& a, const RtRayQuery& q)
 {
     if (q.n == 0 || q.blocks == 0) return true;
-    if (q.lpr > 1) { // segments: the (block size, lanes per ray) pairs of the prepass's ladder
+    if (q.lpr > 1) { // segments
         if (a.landscape != RT_NOMADPLAINS) return false;
-        if (q.bs == RT_PREPASS_BS1 && q.lpr == RT_PREPASS_LPR1) launch_rayquery_seg<RT_PREPASS_BS1, RT_PREPASS_LPR1>(a, q);
-        else if (q.bs == 512 && q.lpr == 32) launch_rayquery_seg<512, 32>(a, q);
-        else if (q.bs == 512 && q.lpr == 8) launch_rayquery_seg<512, 8>(a, q);
-        else if (q.bs == 512 && q.lpr == 4) launch_rayquery_seg<512, 4>(a, q);
-        else return false;
-        return true;
+        return with_segment(q.bs, q.lpr, [&](auto bs_tag, auto lpr_tag) {
+            with_bool(q.steps != nullptr, [&](auto steps_tag) {
+                constexpr int BS = decltype(bs_tag)::value, LPR = decltype(lpr_tag)::value;
+                hipLaunchKernelGGL((k_rayquery_seg<decltype(steps_tag)::value, BS, LPR>), dim3(q.blocks), dim3(BS), 0,
+                                   a.stream, a.consts, a.perm2d, a.grad, q.rays, q.results, q.steps, q.n, q.eye[0],
+                                   q.eye[1], q.eye[2]);
+            });
+        });
     }
-    switch (a.landscape) {
-    case RT_TESTING: launch_rayquery_lanes<RT_TESTING>(a, q); break;
-    case RT_SIMPLE: launch_rayquery_lanes<RT_SIMPLE>(a, q); break;
-    case RT_GREENROCKS: launch_rayquery_lanes<RT_GREENROCKS>(a, q); break;
-    default: launch_rayquery_lanes<RT_NOMADPLAINS>(a, q); break;
-    }
+    // the live-lane count at or below which a wave refills (RT_RAYQ_REFILL; at most 63, so a refill claims >= 1 ray)
+    constexpr uint32_t thr = RT_RAYQ_REFILL < 63 ? RT_RAYQ_REFILL : 63;
+    with_landscape(a, [&](auto l_tag) {
+        with_bool(q.steps != nullptr, [&](auto steps_tag) {
+            hipLaunchKernelGGL((k_rayquery<decltype(l_tag)::value, decltype(steps_tag)::value>), dim3(q.blocks),
+                               dim3(1024), 0, a.stream, a.consts, a.perm2d, a.grad, q.rays, q.results, q.steps, q.n,
+                               q.eye[0], q.eye[1], q.eye[2], q.counter, thr);
+        });
+    });
     return true;
 }
 
@@ -2816,48 +2839,17 @@ __global__ void __launch_bounds__(1024) k_surfquery(const RtConsts* __restrict__
 #endif
 }
 
-SurfArgs surf_args(const RtSurfQuery& q)
+// the one place a SurfArgs is built: surface and shaded queries alike
+SurfArgs surf_args(const float eye[3], const RtMarchParams& m)
 {
-    return SurfArgs{q.eye[0], q.eye[1], q.eye[2], q.t_min, q.t_max, q.stepmod, q.max_steps};
+    return SurfArgs{eye[0], eye[1], eye[2], m.t_min, m.t_max, m.stepmod, m.max_steps};
 }
 
-template <int L, bool STEPS, bool RANGE>
-void launch_surfquery_lanes_as(const RtLaunch& a, const RtSurfQuery& q)
+// f(STEPS, RANGE) as two bool tags
+template <class F>
+void with_steps_range(bool steps, bool range, F f)
 {
-    constexpr uint32_t thr = RT_RAYQ_REFILL < 63 ? RT_RAYQ_REFILL : 63; // as launch_rayquery_lanes
-    hipLaunchKernelGGL((k_surfquery<L, STEPS, RANGE>), dim3(q.blocks), dim3(1024), 0, a.stream, a.consts, a.perm2d,
-                       a.grad, q.rays, q.results, q.steps, q.n, surf_args(q), q.counter, thr);
-}
-
-template <int L>
-void launch_surfquery_lanes(const RtLaunch& a, const RtSurfQuery& q)
-{
-    if (q.steps) {
-        if (q.ray_range) launch_surfquery_lanes_as<L, true, true>(a, q);
-        else launch_surfquery_lanes_as<L, true, false>(a, q);
-    } else {
-        if (q.ray_range) launch_surfquery_lanes_as<L, false, true>(a, q);
-        else launch_surfquery_lanes_as<L, false, false>(a, q);
-    }
-}
-
-template <bool STEPS, bool RANGE, int BS, int LPR>
-void launch_surfquery_seg_as(const RtLaunch& a, const RtSurfQuery& q)
-{
-    hipLaunchKernelGGL((k_surfquery_seg<STEPS, RANGE, BS, LPR>), dim3(q.blocks), dim3(BS), 0, a.stream, a.consts,
-                       a.perm2d, a.grad, q.rays, q.results, q.steps, q.n, surf_args(q));
-}
-
-template <int BS, int LPR>
-void launch_surfquery_seg(const RtLaunch& a, const RtSurfQuery& q)
-{
-    if (q.steps) {
-        if (q.ray_range) launch_surfquery_seg_as<true, true, BS, LPR>(a, q);
-        else launch_surfquery_seg_as<true, false, BS, LPR>(a, q);
-    } else {
-        if (q.ray_range) launch_surfquery_seg_as<false, true, BS, LPR>(a, q);
-        else launch_surfquery_seg_as<false, false, BS, LPR>(a, q);
-    }
+    with_bool(steps, [&](auto steps_tag) { with_bool(range, [&](auto range_tag) { f(steps_tag, range_tag); }); });
 }
 
 } // namespace
@@ -2865,21 +2857,27 @@ void launch_surfquery_seg(const RtLaunch& a, const RtSurfQuery& q)
 bool rt_launch_surfquery(const RtLaunch& a, const RtSurfQuery& q)
 {
     if (q.n == 0 || q.blocks == 0) return true;
-    if (q.lpr > 1) { // segments: the pairs of rt_launch_rayquery
+    const SurfArgs sa = surf_args(q.eye, q.march);
+    if (q.lpr > 1) { // segments
         if (a.landscape != RT_NOMADPLAINS) return false;
-        if (q.bs == RT_PREPASS_BS1 && q.lpr == RT_PREPASS_LPR1) launch_surfquery_seg<RT_PREPASS_BS1, RT_PREPASS_LPR1>(a, q);
-        else if (q.bs == 512 && q.lpr == 32) launch_surfquery_seg<512, 32>(a, q);
-        else if (q.bs == 512 && q.lpr == 8) launch_surfquery_seg<512, 8>(a, q);
-        else if (q.bs == 512 && q.lpr == 4) launch_surfquery_seg<512, 4>(a, q);
-        else return false;
-        return true;
+        return with_segment(q.bs, q.lpr, [&](auto bs_tag, auto lpr_tag) {
+            with_steps_range(q.steps != nullptr, q.march.ray_range, [&](auto steps_tag, auto range_tag) {
+                constexpr int BS = decltype(bs_tag)::value, LPR = decltype(lpr_tag)::value;
+                constexpr bool STEPS = decltype(steps_tag)::value, RANGE = decltype(range_tag)::value;
+                hipLaunchKernelGGL((k_surfquery_seg<STEPS, RANGE, BS, LPR>), dim3(q.blocks), dim3(BS), 0, a.stream,
+                                   a.consts, a.perm2d, a.grad, q.rays, q.results, q.steps, q.n, sa);
+            });
+        });
     }
-    switch (a.landscape) {
-    case RT_TESTING: launch_surfquery_lanes<RT_TESTING>(a, q); break;
-    case RT_SIMPLE: launch_surfquery_lanes<RT_SIMPLE>(a, q); break;
-    case RT_GREENROCKS: launch_surfquery_lanes<RT_GREENROCKS>(a, q); break;
-    default: launch_surfquery_lanes<RT_NOMADPLAINS>(a, q); break;
-    }
+    constexpr uint32_t thr = RT_RAYQ_REFILL < 63 ? RT_RAYQ_REFILL : 63; // as rt_launch_rayquery
+    with_landscape(a, [&](auto l_tag) {
+        with_steps_range(q.steps != nullptr, q.march.ray_range, [&](auto steps_tag, auto range_tag) {
+            constexpr bool STEPS = decltype(steps_tag)::value, RANGE = decltype(range_tag)::value;
+            hipLaunchKernelGGL((k_surfquery<decltype(l_tag)::value, STEPS, RANGE>), dim3(q.blocks), dim3(1024), 0,
+                               a.stream, a.consts, a.perm2d, a.grad, q.rays, q.results, q.steps, q.n, sa, q.counter,
+                               thr);
+        });
+    });
     return true;
 }
 
@@ -3041,39 +3039,22 @@ __global__ void __launch_bounds__(1024) k_shadequery(const RtConsts* __restrict_
 #endif
 }
 
-template <int L, bool STEPS, bool RANGE>
-void launch_shadequery_as(const RtLaunch& a, const RtShadeQuery& q)
-{
-    constexpr uint32_t thr = RT_SHADEQ_REFILL < 63 ? RT_SHADEQ_REFILL : 63;
-    const SurfArgs sa{q.eye[0], q.eye[1], q.eye[2], q.t_min, q.t_max, q.stepmod, q.max_steps};
-    hipLaunchKernelGGL((k_shadequery<L, STEPS, RANGE>), dim3(q.blocks), dim3(1024), 0, a.stream, a.consts, a.perm2d,
-                       a.grad, q.rays, q.results, q.rgba8, q.steps, q.n, sa, q.counter, thr);
-}
-
-template <int L>
-void launch_shadequery(const RtLaunch& a, const RtShadeQuery& q)
-{
-    if (q.steps) {
-        if (q.ray_range) launch_shadequery_as<L, true, true>(a, q);
-        else launch_shadequery_as<L, true, false>(a, q);
-    } else {
-        if (q.ray_range) launch_shadequery_as<L, false, true>(a, q);
-        else launch_shadequery_as<L, false, false>(a, q);
-    }
-}
-
 } // namespace
 
 bool rt_launch_shadequery(const RtLaunch& a, const RtShadeQuery& q)
 {
     if (q.n == 0 || q.blocks == 0) return true;
     if (!q.counter || (!q.results && !q.rgba8)) return false;
-    switch (a.landscape) {
-    case RT_TESTING: launch_shadequery<RT_TESTING>(a, q); break;
-    case RT_SIMPLE: launch_shadequery<RT_SIMPLE>(a, q); break;
-    case RT_GREENROCKS: launch_shadequery<RT_GREENROCKS>(a, q); break;
-    default: launch_shadequery<RT_NOMADPLAINS>(a, q); break;
-    }
+    constexpr uint32_t thr = RT_SHADEQ_REFILL < 63 ? RT_SHADEQ_REFILL : 63;
+    const SurfArgs sa = surf_args(q.eye, q.march);
+    with_landscape(a, [&](auto l_tag) {
+        with_steps_range(q.steps != nullptr, q.march.ray_range, [&](auto steps_tag, auto range_tag) {
+            constexpr bool STEPS = decltype(steps_tag)::value, RANGE = decltype(range_tag)::value;
+            hipLaunchKernelGGL((k_shadequery<decltype(l_tag)::value, STEPS, RANGE>), dim3(q.blocks), dim3(1024), 0,
+                               a.stream, a.consts, a.perm2d, a.grad, q.rays, q.results, q.rgba8, q.steps, q.n, sa,
+                               q.counter, thr);
+        });
+    });
     return true;
 }
 
@@ -3196,26 +3177,18 @@ void launch_fieldquery(const RtLaunch& a, const RtFieldQuery& q)
                        a.grad, q.results, q.occupancy, g, e);
 }
 
-template <int L>
-void launch_fieldquery_l(const RtLaunch& a, const RtFieldQuery& q)
-{
-    // occupancy alone needs no normal
-    if (q.normal && q.results) launch_fieldquery<L, true>(a, q);
-    else launch_fieldquery<L, false>(a, q);
-}
-
 } // namespace
 
 bool rt_launch_fieldquery(const RtLaunch& a, const RtFieldQuery& q)
 {
     if (q.n == 0 || q.blocks == 0) return true;
     if (q.points ? !q.results : ((!q.results && !q.occupancy) || q.rows == 0)) return false;
-    switch (a.landscape) {
-    case RT_TESTING: launch_fieldquery_l<RT_TESTING>(a, q); break;
-    case RT_SIMPLE: launch_fieldquery_l<RT_SIMPLE>(a, q); break;
-    case RT_GREENROCKS: launch_fieldquery_l<RT_GREENROCKS>(a, q); break;
-    default: launch_fieldquery_l<RT_NOMADPLAINS>(a, q); break;
-    }
+    with_landscape(a, [&](auto l_tag) {
+        // occupancy alone needs no normal
+        with_bool(q.normal && q.results, [&](auto normal_tag) {
+            launch_fieldquery<decltype(l_tag)::value, decltype(normal_tag)::value>(a, q);
+        });
+    });
     return true;
 }
 

@@ -1,8 +1,9 @@
 // rt_rayquery.h -- host-only decisions of rt_terrain_trace_rays, rt_terrain_trace_surface,
 // rt_terrain_shade_rays and the field queries rt_terrain_sample_field / rt_terrain_sample_lattice
-// (include/frosttrace.h): the option blocks' validation and the choice of the kernel shape, its lanes per ray,
-// its strips and its grid.  No HIP in here: tests/tools/rayquery_check.cpp, surfquery_check.cpp,
-// shadequery_check.cpp and fieldquery_check.cpp drive it stand-alone under ASan + UBSan.
+// (include/frosttrace.h): the option blocks' validation, the choice of the kernel shape, its lanes per ray,
+// its strips and its grid, and the layout of the host forms' device block.  No HIP in here:
+// tests/tools/rayquery_check.cpp, surfquery_check.cpp, shadequery_check.cpp, fieldquery_check.cpp and
+// querylayout_check.cpp drive it stand-alone under ASan + UBSan.
 #pragma once
 
 #include <cstddef>
@@ -28,33 +29,46 @@ enum Shape { SEGMENTS = 0, LANES = 1 };
 // 2.52 at 262,144: the crossing lies between 131,072 and 196,608.
 constexpr int kAutoSegmentsMax = 128 * 1024;
 
+// the prefix the three option blocks share: size, flags, eye[3], max_blocks
 struct Options {
     uint32_t flags = 0;
     float eye[3] = {0.0f, 0.0f, 0.0f};
     uint32_t max_blocks = 0;
 };
+using FieldOptions = Options;
 
-// `opt` is the caller's rt_ray_options (may be null: the defaults), read through its size field only as far
-// as the first version reaches; a larger size is a later version whose extra fields this build ignores.
-inline int parse_options(const void* opt, Options* out, const char** why)
+// The version-1 prefix of the caller's option block `opt` (not null), read through its size field: a size below
+// `size_v1`, the family's first version, is an error (false, nothing read beyond the size); a larger one is a
+// later version whose extra fields this build ignores.
+inline bool parse_prefix(const void* opt, uint32_t size_v1, Options* out)
 {
-    *out = Options{};
-    if (!opt) return OK;
     uint32_t size;
     std::memcpy(&size, opt, 4);
-    if (size < kOptSizeV1) {
-        *why = "rt_ray_options.size is smaller than the struct's first version";
-        return INVALID;
-    }
+    if (size < size_v1) return false;
     const char* p = static_cast<const char*>(opt);
     std::memcpy(&out->flags, p + 4, 4);
     std::memcpy(out->eye, p + 8, 12);
     std::memcpy(&out->max_blocks, p + 20, 4);
-    if ((out->flags & kForceSegments) && (out->flags & kForceLanes)) {
-        *why = "RT_RAYS_FORCE_SEGMENTS and RT_RAYS_FORCE_LANES are both set";
+    return true;
+}
+
+inline bool both_shapes_forced(uint32_t flags, const char** why)
+{
+    if (!(flags & kForceSegments) || !(flags & kForceLanes)) return false;
+    *why = "RT_RAYS_FORCE_SEGMENTS and RT_RAYS_FORCE_LANES are both set";
+    return true;
+}
+
+// `opt` is the caller's rt_ray_options (may be null: the defaults), read as far as the first version reaches.
+inline int parse_options(const void* opt, Options* out, const char** why)
+{
+    *out = Options{};
+    if (!opt) return OK;
+    if (!parse_prefix(opt, kOptSizeV1, out)) {
+        *why = "rt_ray_options.size is smaller than the struct's first version";
         return INVALID;
     }
-    return OK;
+    return both_shapes_forced(out->flags, why) ? INVALID : OK;
 }
 
 inline int check_count(int n, const char** why)
@@ -135,37 +149,25 @@ constexpr float kSurfTMin = 0.01f, kSurfTMax = 5000.0f, kSurfStepmod = 1.0f;
 // near 119,000 rays; the rule sits just below it.
 constexpr int kSurfAutoSegmentsMax = 112 * 1024;
 
-struct SurfOptions {
-    uint32_t flags = 0;
-    float eye[3] = {0.0f, 0.0f, 0.0f};
-    uint32_t max_blocks = 0;
+struct SurfOptions : Options {
     float t_min = kSurfTMin, t_max = kSurfTMax, stepmod = kSurfStepmod;
     uint32_t max_steps = 0; // 0: unbounded
 };
 
 inline bool finite_f(float x) { return x - x == 0.0f; }
 
-// `opt` is the caller's rt_surface_options (may be null: the defaults), read through its size field only as far
-// as the first version reaches; a larger size is a later version whose extra fields this build ignores.  The
-// four trailing fields count with RT_SURFACE_PARAMS only.
+// `opt` is the caller's rt_surface_options (may be null: the defaults), read as far as the first version
+// reaches.  The four trailing fields count with RT_SURFACE_PARAMS only.
 inline int parse_surface_options(const void* opt, SurfOptions* out, const char** why)
 {
     *out = SurfOptions{};
     if (!opt) return OK;
-    uint32_t size;
-    std::memcpy(&size, opt, 4);
-    if (size < kSurfOptSizeV1) {
+    if (!parse_prefix(opt, kSurfOptSizeV1, out)) {
         *why = "rt_surface_options.size is smaller than the struct's first version";
         return INVALID;
     }
+    if (both_shapes_forced(out->flags, why)) return INVALID;
     const char* p = static_cast<const char*>(opt);
-    std::memcpy(&out->flags, p + 4, 4);
-    std::memcpy(out->eye, p + 8, 12);
-    std::memcpy(&out->max_blocks, p + 20, 4);
-    if ((out->flags & kForceSegments) && (out->flags & kForceLanes)) {
-        *why = "RT_RAYS_FORCE_SEGMENTS and RT_RAYS_FORCE_LANES are both set";
-        return INVALID;
-    }
     if (out->flags & kSurfParams) {
         std::memcpy(&out->t_min, p + 24, 4);
         std::memcpy(&out->t_max, p + 28, 4);
@@ -223,28 +225,15 @@ constexpr uint32_t kFieldRows = 8u;
 // waves of a field kernel's block (1024 threads)
 constexpr uint32_t kFieldWaves = 16u;
 
-struct FieldOptions {
-    uint32_t flags = 0;
-    float eye[3] = {0.0f, 0.0f, 0.0f};
-    uint32_t max_blocks = 0;
-};
-
-// `opt` is the caller's rt_field_options (may be null: the defaults), read through its size field only as far
-// as the first version reaches.
+// `opt` is the caller's rt_field_options (may be null: the defaults), read as far as the first version reaches.
 inline int parse_field_options(const void* opt, FieldOptions* out, const char** why)
 {
     *out = FieldOptions{};
     if (!opt) return OK;
-    uint32_t size;
-    std::memcpy(&size, opt, 4);
-    if (size < kFieldOptSizeV1) {
+    if (!parse_prefix(opt, kFieldOptSizeV1, out)) {
         *why = "rt_field_options.size is smaller than the struct's first version";
         return INVALID;
     }
-    const char* p = static_cast<const char*>(opt);
-    std::memcpy(&out->flags, p + 4, 4);
-    std::memcpy(out->eye, p + 8, 12);
-    std::memcpy(&out->max_blocks, p + 20, 4);
     if (out->flags & ~(kEye | kFieldNormal)) {
         *why = "rt_field_options.flags has bits other than RT_RAYS_EYE and RT_FIELD_NORMAL";
         return INVALID;
@@ -321,6 +310,39 @@ inline FieldPlan plan_field_lattice(const uint32_t dims[3], bool nomadplains, ui
     const uint32_t strips = lattice_strips(dims, p.rows);
     p.blocks = field_grid((strips + kFieldWaves - 1u) / kFieldWaves, max_blocks, cus);
     return p;
+}
+
+// ---- the host forms' device block: one allocation holding a query's arrays ----
+
+// bytes per element of the arrays: a packed ray, a packed point, a ray result, a surface or shaded result, an
+// RGBA8 pixel, a ray's or surface ray's step count, a shaded ray's two
+constexpr size_t kRayBytes = 32, kPointBytes = 16, kRayResultBytes = 16, kSurfResultBytes = 32, kPixelBytes = 4,
+                 kStepsBytes = 4, kShadeStepsBytes = 8;
+// a field result's bytes per point: the density, or with the normal {n.xyz, d}
+inline size_t field_stride(uint32_t flags) { return (flags & kFieldNormal) ? 16 : 4; }
+// a lattice's occupancy: one bit a point, ceil(nx / 32) words a row
+inline size_t occupancy_bytes(const uint32_t dims[3])
+{
+    return (size_t)((dims[0] + 31u) / 32u) * dims[1] * dims[2] * 4;
+}
+
+constexpr int kBlockParts = 4;
+struct BlockLayout {
+    size_t offset[kBlockParts] = {0, 0, 0, 0};
+    size_t total = 0;
+};
+
+// parts <= kBlockParts sizes in bytes, in order; 0: the part is absent and takes no space.  Every present part
+// starts at a multiple of 16 (the kernels' float4 accesses), so the total is the present parts' sizes, each
+// rounded up to 16.
+inline BlockLayout block_layout(const size_t* bytes, int parts)
+{
+    BlockLayout l;
+    for (int i = 0; i < parts && i < kBlockParts; ++i) {
+        l.offset[i] = l.total;
+        l.total += (bytes[i] + 15) / 16 * 16;
+    }
+    return l;
 }
 
 // point i of a packed field query: x y z _

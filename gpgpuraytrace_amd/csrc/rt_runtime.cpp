@@ -2800,92 +2800,117 @@ int sync_query_consts(rt_device dev, Shader* s, float default_eye[3], const floa
     return RT_OK;
 }
 
-// plan and enqueue one query of n >= 1 rays on the device stream (no host synchronisation)
-int trace_rays_enqueue(rt_compute c, const void* rays_device, int n, const rtq::Options& o, void* results_device,
-                       void* steps_device)
+// The launch of a query on `c`, pointed at the query's own device copies of the constants and gradients, brought up
+// to date first; eye: the kernel's eye argument, the option's if it has one, else the compute's.  sky_eye (shaded
+// queries): the constants' copy carries the option's eye too, for the sky.
+int query_prepare(rt_compute c, const rtq::Options& o, bool sky_eye, RtLaunch* a, float eye[3])
 {
-    rt_device dev = c->dev;
-    Shader* s = c->shader;
-    float eye[3];
-    if (int rc = sync_query_consts(dev, s, eye)) return rc;
-    if (o.flags & rtq::kEye) memcpy(eye, o.eye, sizeof(eye));
-    rtq::Plan p;
-    const char* why = "";
-    if (int rc = rtq::plan(n, s->landscape == RT_NOMADPLAINS, o.flags, o.max_blocks, dev->num_cus - dev->reserve_cus,
-                           RT_PREPASS_BS1, RT_PREPASS_LPR1, &p, &why))
-        return fail(rc, "rt_terrain_trace_rays: %s", why);
-    RtLaunch a = make_launch(dev, s);
-    a.consts = s->query.d_consts;
-    a.grad = s->query.d_grad;
-    RtRayQuery q{};
-    q.rays = (const float4*)rays_device;
-    q.results = (float4*)results_device;
-    q.steps = (uint32_t*)steps_device;
-    q.n = (uint32_t)n;
-    memcpy(q.eye, eye, sizeof(eye));
-    q.bs = p.bs;
-    q.lpr = p.lpr;
-    q.blocks = p.blocks;
-    if (p.shape == rtq::LANES) {
-        if (!dev->rq_counter) HIP_TRY(hipMalloc(&dev->rq_counter, 64));
-        HIP_TRY(hipMemsetAsync(dev->rq_counter, 0, 4, dev->stream));
-        q.counter = dev->rq_counter;
-    }
-    if (!rt_launch_rayquery(a, q)) return fail(RT_ERR_UNSUPPORTED, "rt_terrain_trace_rays: no kernel for this shape");
+    const float* opt_eye = (o.flags & rtq::kEye) ? o.eye : nullptr;
+    if (int rc = sync_query_consts(c->dev, c->shader, eye, sky_eye ? opt_eye : nullptr)) return rc;
+    if (opt_eye) memcpy(eye, opt_eye, 3 * sizeof(float));
+    *a = make_launch(c->dev, c->shader);
+    a->consts = c->shader->query.d_consts;
+    a->grad = c->shader->query.d_grad;
+    return RT_OK;
+}
+
+// the lane kernels' claim counter, allocated on first use and zeroed on the stream before every launch
+int arm_counter(rt_device dev, uint32_t** counter)
+{
+    if (!dev->rq_counter) HIP_TRY(hipMalloc(&dev->rq_counter, 64));
+    HIP_TRY(hipMemsetAsync(dev->rq_counter, 0, 4, dev->stream));
+    *counter = dev->rq_counter;
+    return RT_OK;
+}
+
+// after rt_launch_*: `launched` false is a query without a kernel
+int query_launched(bool launched, const char* no_kernel)
+{
+    if (!launched) return fail(RT_ERR_UNSUPPORTED, "%s", no_kernel);
     HIP_TRY(hipGetLastError());
     return RT_OK;
 }
 
-// the checks both forms share, in the order the header gives; *o: the parsed options
-int trace_rays_check(rt_compute c, int n, const rt_ray_options* opt, rtq::Options* o)
+int cus_of(rt_device dev) { return dev->num_cus - dev->reserve_cus; }
+
+RtMarchParams march_params(const rtq::SurfOptions& o)
+{
+    return RtMarchParams{o.t_min, o.t_max, o.stepmod, rtq::surface_max_steps(o.max_steps),
+                         (o.flags & rtq::kSurfRayRange) != 0};
+}
+
+// What a query family brings to query_entry.
+template <class Opt>
+struct QueryFamily {
+    const char* name;    // begins the messages about the count, the options and the family's clause
+    const char* counted; // "ray" / "point" in the count's message; null: the entry point takes no count (a lattice)
+    int (*parse)(const void*, Opt*, const char**);
+};
+
+// Every query entry point: the checks in the order the header gives, then run(o, n) on the compute's device.
+// clause(o, &n): the family's own check (it reports its failure itself; a lattice sets n).  missing: the message
+// about absent arrays, or null; it counts for n > 0 only.
+template <class Opt, class Clause, class Run>
+int query_entry(rt_compute c, const QueryFamily<Opt>& f, int count, const void* opt, Clause clause, const char* missing,
+                Run run)
 {
     if (!c) return fail(RT_ERR_INVALID, "null compute");
     const char* why = "";
-    if (int rc = rtq::check_count(n, &why)) return fail(rc, "rt_terrain_trace_rays: %s", why);
-    if (int rc = rtq::parse_options(opt, o, &why)) return fail(rc, "rt_terrain_trace_rays: %s", why);
+    if (f.counted && rtq::check_count(count, &why))
+        return fail(RT_ERR_INVALID, "%s: the %s count must be 0..2^26", f.name, f.counted);
+    Opt o;
+    if (int rc = f.parse(opt, &o, &why)) return fail(rc, "%s: %s", f.name, why);
     if (!c->shader) return fail(RT_ERR_STATE, "no current shader");
-    if ((o->flags & rtq::kForceSegments) && c->shader->landscape != RT_NOMADPLAINS)
-        return fail(RT_ERR_UNSUPPORTED, "rt_terrain_trace_rays: the segment shape exists for nomadplains only");
-    return RT_OK;
-}
-
-} // namespace
-
-extern "C" int rt_terrain_trace_rays_device(rt_compute c, const void* rays_device, int n, const rt_ray_options* opt,
-                                            void* results_device, void* steps_device)
-{
-    rtq::Options o;
-    if (int rc = trace_rays_check(c, n, opt, &o)) return rc;
-    if (n > 0 && (!rays_device || !results_device)) return fail(RT_ERR_INVALID, "rt_terrain_trace_rays_device: null rays or results");
+    uint32_t n = (uint32_t)count;
+    if (int rc = clause(o, &n)) return rc;
+    if (n > 0 && missing) return fail(RT_ERR_INVALID, "%s", missing);
     if (int rc = check_texture(c->shader)) return rc;
     if (int rc = host_flag_check(c->dev)) return rc;
     if (n == 0) return RT_OK;
     HIP_TRY(hipSetDevice(c->dev->ordinal));
-    return trace_rays_enqueue(c, rays_device, n, o, results_device, steps_device);
+    return run(o, n);
 }
 
-extern "C" int rt_terrain_trace_rays(rt_compute c, const float* origins, const float* dirs, int n,
-                                     const rt_ray_options* opt, float* results, uint32_t* steps)
+// the ray and surface queries' clause
+template <class Opt>
+auto segments_clause(rt_compute c, const char* name)
 {
-    rtq::Options o;
-    if (int rc = trace_rays_check(c, n, opt, &o)) return rc;
-    if (n > 0 && (!origins || !dirs || !results)) return fail(RT_ERR_INVALID, "rt_terrain_trace_rays: null origins, dirs or results");
-    if (int rc = check_texture(c->shader)) return rc;
-    if (int rc = host_flag_check(c->dev)) return rc;
-    if (n == 0) return RT_OK;
-    rt_device dev = c->dev;
-    HIP_TRY(hipSetDevice(dev->ordinal));
-    // one device block: the packed rays, the results, the step counts
-    const size_t nr = (size_t)n, rays_b = nr * 32, res_b = nr * 16, steps_b = steps ? nr * 4 : 0;
-    std::vector<float> packed(nr * 8);
-    rtq::pack(origins, dirs, n, packed.data());
+    return [=](const Opt& o, uint32_t*) -> int {
+        if ((o.flags & rtq::kForceSegments) && c->shader->landscape != RT_NOMADPLAINS)
+            return fail(RT_ERR_UNSUPPORTED, "%s: the segment shape exists for nomadplains only", name);
+        return RT_OK;
+    };
+}
+
+// One array of a blocking ("host") form: `bytes` of the device block (0: the array is absent), uploaded from src
+// before the query and downloaded to dst after it, each if set.
+struct HostPart {
+    size_t bytes;
+    const void* src;
+    void* dst;
+};
+
+// A host form: one device block laid out by rtq::block_layout, the uploads, enqueue(at) with the parts' device
+// addresses (null for an absent part), the downloads and a synchronise, all on the device stream.
+template <int N, class Enqueue>
+int host_form(rt_device dev, const HostPart (&parts)[N], Enqueue enqueue)
+{
+    static_assert(N <= rtq::kBlockParts, "a part more than the layout holds");
+    size_t bytes[N];
+    for (int i = 0; i < N; ++i) bytes[i] = parts[i].bytes;
+    const rtq::BlockLayout lay = rtq::block_layout(bytes, N);
     char* d = nullptr;
-    HIP_TRY(hipMalloc(&d, rays_b + res_b + steps_b));
+    HIP_TRY(hipMalloc(&d, lay.total));
+    char* at[N];
+    for (int i = 0; i < N; ++i) at[i] = bytes[i] ? d + lay.offset[i] : nullptr;
     auto run = [&]() -> int {
-        HIP_TRY(hipMemcpyAsync(d, packed.data(), rays_b, hipMemcpyHostToDevice, dev->stream));
-        if (int rc = trace_rays_enqueue(c, d, n, o, d + rays_b, steps ? d + rays_b + res_b : nullptr)) return rc;
-        HIP_TRY(hipMemcpyAsync(results, d + rays_b, res_b, hipMemcpyDeviceToHost, dev->stream));
-        if (steps) HIP_TRY(hipMemcpyAsync(steps, d + rays_b + res_b, steps_b, hipMemcpyDeviceToHost, dev->stream));
+        for (int i = 0; i < N; ++i)
+            if (at[i] && parts[i].src)
+                HIP_TRY(hipMemcpyAsync(at[i], parts[i].src, bytes[i], hipMemcpyHostToDevice, dev->stream));
+        if (int rc = enqueue(at)) return rc;
+        for (int i = 0; i < N; ++i)
+            if (at[i] && parts[i].dst)
+                HIP_TRY(hipMemcpyAsync(parts[i].dst, at[i], bytes[i], hipMemcpyDeviceToHost, dev->stream));
         HIP_TRY(hipStreamSynchronize(dev->stream));
         return RT_OK;
     };
@@ -2893,6 +2918,76 @@ extern "C" int rt_terrain_trace_rays(rt_compute c, const float* origins, const f
     if (rc) (void)hipStreamSynchronize(dev->stream); // whatever was queued is over before the block is freed
     (void)hipFree(d);
     return rc;
+}
+
+// the rays of a surface or shaded host form, packed; the spare words are the ranges exactly when it was given some
+std::vector<float> pack_surface_rays(const float* origins, const float* dirs, const float* ranges, uint32_t n,
+                                     rtq::SurfOptions* o)
+{
+    if (ranges) o->flags |= rtq::kSurfRayRange;
+    else o->flags &= ~rtq::kSurfRayRange;
+    std::vector<float> packed((size_t)n * 8);
+    rtq::pack(origins, dirs, (int)n, packed.data());
+    if (ranges) rtq::pack_ranges(ranges, (int)n, packed.data());
+    return packed;
+}
+
+// plan and enqueue one query of n >= 1 rays on the device stream (no host synchronisation)
+int trace_rays_enqueue(rt_compute c, const void* rays_device, uint32_t n, const rtq::Options& o, void* results_device,
+                       void* steps_device)
+{
+    rt_device dev = c->dev;
+    RtLaunch a;
+    RtRayQuery q{};
+    if (int rc = query_prepare(c, o, false, &a, q.eye)) return rc;
+    rtq::Plan p;
+    const char* why = "";
+    if (int rc = rtq::plan((int)n, a.landscape == RT_NOMADPLAINS, o.flags, o.max_blocks, cus_of(dev), RT_PREPASS_BS1,
+                           RT_PREPASS_LPR1, &p, &why))
+        return fail(rc, "rt_terrain_trace_rays: %s", why);
+    q.rays = (const float4*)rays_device;
+    q.results = (float4*)results_device;
+    q.steps = (uint32_t*)steps_device;
+    q.n = n;
+    q.bs = p.bs;
+    q.lpr = p.lpr;
+    q.blocks = p.blocks;
+    if (p.shape == rtq::LANES)
+        if (int rc = arm_counter(dev, &q.counter)) return rc;
+    return query_launched(rt_launch_rayquery(a, q), "rt_terrain_trace_rays: no kernel for this shape");
+}
+
+const QueryFamily<rtq::Options> kRayFamily{"rt_terrain_trace_rays", "ray", rtq::parse_options};
+
+} // namespace
+
+extern "C" int rt_terrain_trace_rays_device(rt_compute c, const void* rays_device, int n, const rt_ray_options* opt,
+                                            void* results_device, void* steps_device)
+{
+    return query_entry(
+        c, kRayFamily, n, opt, segments_clause<rtq::Options>(c, kRayFamily.name),
+        !rays_device || !results_device ? "rt_terrain_trace_rays_device: null rays or results" : nullptr,
+        [&](const rtq::Options& o, uint32_t nr) {
+            return trace_rays_enqueue(c, rays_device, nr, o, results_device, steps_device);
+        });
+}
+
+extern "C" int rt_terrain_trace_rays(rt_compute c, const float* origins, const float* dirs, int n,
+                                     const rt_ray_options* opt, float* results, uint32_t* steps)
+{
+    return query_entry(
+        c, kRayFamily, n, opt, segments_clause<rtq::Options>(c, kRayFamily.name),
+        !origins || !dirs || !results ? "rt_terrain_trace_rays: null origins, dirs or results" : nullptr,
+        [&](const rtq::Options& o, uint32_t nr) {
+            std::vector<float> packed((size_t)nr * 8);
+            rtq::pack(origins, dirs, n, packed.data());
+            // one device block: the packed rays, the results, the step counts
+            const HostPart parts[] = {{nr * rtq::kRayBytes, packed.data(), nullptr},
+                                      {nr * rtq::kRayResultBytes, nullptr, results},
+                                      {steps ? nr * rtq::kStepsBytes : 0, nullptr, steps}};
+            return host_form(c->dev, parts,
+                             [&](char* const* at) { return trace_rays_enqueue(c, at[0], nr, o, at[1], at[2]); });
+        });
 }
 
 // ---------------------------------------------------------------------------
@@ -2900,107 +2995,61 @@ extern "C" int rt_terrain_trace_rays(rt_compute c, const float* origins, const f
 // normal at each hit (include/frosttrace.h).  The query state (Shader::query, the claim counter) is the ray queries'.
 namespace {
 
-int trace_surface_enqueue(rt_compute c, const void* rays_device, int n, const rtq::SurfOptions& o, void* results_device,
-                          void* steps_device)
+int trace_surface_enqueue(rt_compute c, const void* rays_device, uint32_t n, const rtq::SurfOptions& o,
+                          void* results_device, void* steps_device)
 {
     rt_device dev = c->dev;
-    Shader* s = c->shader;
-    float eye[3];
-    if (int rc = sync_query_consts(dev, s, eye)) return rc;
-    if (o.flags & rtq::kEye) memcpy(eye, o.eye, sizeof(eye));
+    RtLaunch a;
+    RtSurfQuery q{};
+    if (int rc = query_prepare(c, o, false, &a, q.eye)) return rc;
     rtq::Plan p;
     const char* why = "";
-    if (int rc = rtq::plan_surface(n, s->landscape == RT_NOMADPLAINS, o.flags, o.max_blocks, dev->num_cus - dev->reserve_cus,
+    if (int rc = rtq::plan_surface((int)n, a.landscape == RT_NOMADPLAINS, o.flags, o.max_blocks, cus_of(dev),
                                    RT_PREPASS_BS1, RT_PREPASS_LPR1, &p, &why))
         return fail(rc, "rt_terrain_trace_surface: %s", why);
-    RtLaunch a = make_launch(dev, s);
-    a.consts = s->query.d_consts;
-    a.grad = s->query.d_grad;
-    RtSurfQuery q{};
     q.rays = (const float4*)rays_device;
     q.results = (float4*)results_device;
     q.steps = (uint32_t*)steps_device;
-    q.n = (uint32_t)n;
-    memcpy(q.eye, eye, sizeof(eye));
+    q.n = n;
     q.bs = p.bs;
     q.lpr = p.lpr;
     q.blocks = p.blocks;
-    q.t_min = o.t_min;
-    q.t_max = o.t_max;
-    q.stepmod = o.stepmod;
-    q.max_steps = rtq::surface_max_steps(o.max_steps);
-    q.ray_range = (o.flags & rtq::kSurfRayRange) != 0;
-    if (p.shape == rtq::LANES) {
-        if (!dev->rq_counter) HIP_TRY(hipMalloc(&dev->rq_counter, 64));
-        HIP_TRY(hipMemsetAsync(dev->rq_counter, 0, 4, dev->stream));
-        q.counter = dev->rq_counter;
-    }
-    if (!rt_launch_surfquery(a, q)) return fail(RT_ERR_UNSUPPORTED, "rt_terrain_trace_surface: no kernel for this shape");
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
+    q.march = march_params(o);
+    if (p.shape == rtq::LANES)
+        if (int rc = arm_counter(dev, &q.counter)) return rc;
+    return query_launched(rt_launch_surfquery(a, q), "rt_terrain_trace_surface: no kernel for this shape");
 }
 
-// the checks both forms share, in the order the header gives; *o: the parsed options
-int trace_surface_check(rt_compute c, int n, const rt_surface_options* opt, rtq::SurfOptions* o)
-{
-    if (!c) return fail(RT_ERR_INVALID, "null compute");
-    const char* why = "";
-    if (int rc = rtq::check_count(n, &why)) return fail(rc, "rt_terrain_trace_surface: %s", why);
-    if (int rc = rtq::parse_surface_options(opt, o, &why)) return fail(rc, "rt_terrain_trace_surface: %s", why);
-    if (!c->shader) return fail(RT_ERR_STATE, "no current shader");
-    if ((o->flags & rtq::kForceSegments) && c->shader->landscape != RT_NOMADPLAINS)
-        return fail(RT_ERR_UNSUPPORTED, "rt_terrain_trace_surface: the segment shape exists for nomadplains only");
-    return RT_OK;
-}
+const QueryFamily<rtq::SurfOptions> kSurfFamily{"rt_terrain_trace_surface", "ray", rtq::parse_surface_options};
 
 } // namespace
 
 extern "C" int rt_terrain_trace_surface_device(rt_compute c, const void* rays_device, int n, const rt_surface_options* opt,
                                                void* results_device, void* steps_device)
 {
-    rtq::SurfOptions o;
-    if (int rc = trace_surface_check(c, n, opt, &o)) return rc;
-    if (n > 0 && (!rays_device || !results_device)) return fail(RT_ERR_INVALID, "rt_terrain_trace_surface_device: null rays or results");
-    if (int rc = check_texture(c->shader)) return rc;
-    if (int rc = host_flag_check(c->dev)) return rc;
-    if (n == 0) return RT_OK;
-    HIP_TRY(hipSetDevice(c->dev->ordinal));
-    return trace_surface_enqueue(c, rays_device, n, o, results_device, steps_device);
+    return query_entry(
+        c, kSurfFamily, n, opt, segments_clause<rtq::SurfOptions>(c, kSurfFamily.name),
+        !rays_device || !results_device ? "rt_terrain_trace_surface_device: null rays or results" : nullptr,
+        [&](const rtq::SurfOptions& o, uint32_t nr) {
+            return trace_surface_enqueue(c, rays_device, nr, o, results_device, steps_device);
+        });
 }
 
 extern "C" int rt_terrain_trace_surface(rt_compute c, const float* origins, const float* dirs, const float* ranges, int n,
                                         const rt_surface_options* opt, float* results, uint32_t* steps)
 {
-    rtq::SurfOptions o;
-    if (int rc = trace_surface_check(c, n, opt, &o)) return rc;
-    if (n > 0 && (!origins || !dirs || !results)) return fail(RT_ERR_INVALID, "rt_terrain_trace_surface: null origins, dirs or results");
-    if (int rc = check_texture(c->shader)) return rc;
-    if (int rc = host_flag_check(c->dev)) return rc;
-    if (n == 0) return RT_OK;
-    // the host form packs the rays itself, so the spare words are the ranges exactly when it was given some
-    if (ranges) o.flags |= rtq::kSurfRayRange;
-    else o.flags &= ~rtq::kSurfRayRange;
-    rt_device dev = c->dev;
-    HIP_TRY(hipSetDevice(dev->ordinal));
-    // one device block: the packed rays, the results, the step counts
-    const size_t nr = (size_t)n, rays_b = nr * 32, res_b = nr * 32, steps_b = steps ? nr * 4 : 0;
-    std::vector<float> packed(nr * 8);
-    rtq::pack(origins, dirs, n, packed.data());
-    if (ranges) rtq::pack_ranges(ranges, n, packed.data());
-    char* d = nullptr;
-    HIP_TRY(hipMalloc(&d, rays_b + res_b + steps_b));
-    auto run = [&]() -> int {
-        HIP_TRY(hipMemcpyAsync(d, packed.data(), rays_b, hipMemcpyHostToDevice, dev->stream));
-        if (int rc = trace_surface_enqueue(c, d, n, o, d + rays_b, steps ? d + rays_b + res_b : nullptr)) return rc;
-        HIP_TRY(hipMemcpyAsync(results, d + rays_b, res_b, hipMemcpyDeviceToHost, dev->stream));
-        if (steps) HIP_TRY(hipMemcpyAsync(steps, d + rays_b + res_b, steps_b, hipMemcpyDeviceToHost, dev->stream));
-        HIP_TRY(hipStreamSynchronize(dev->stream));
-        return RT_OK;
-    };
-    const int rc = run();
-    if (rc) (void)hipStreamSynchronize(dev->stream); // whatever was queued is over before the block is freed
-    (void)hipFree(d);
-    return rc;
+    return query_entry(
+        c, kSurfFamily, n, opt, segments_clause<rtq::SurfOptions>(c, kSurfFamily.name),
+        !origins || !dirs || !results ? "rt_terrain_trace_surface: null origins, dirs or results" : nullptr,
+        [&](rtq::SurfOptions o, uint32_t nr) {
+            const std::vector<float> packed = pack_surface_rays(origins, dirs, ranges, nr, &o);
+            // one device block: the packed rays, the results, the step counts
+            const HostPart parts[] = {{nr * rtq::kRayBytes, packed.data(), nullptr},
+                                      {nr * rtq::kSurfResultBytes, nullptr, results},
+                                      {steps ? nr * rtq::kStepsBytes : 0, nullptr, steps}};
+            return host_form(c->dev, parts,
+                             [&](char* const* at) { return trace_surface_enqueue(c, at[0], nr, o, at[1], at[2]); });
+        });
 }
 
 // ---------------------------------------------------------------------------
@@ -3008,55 +3057,41 @@ extern "C" int rt_terrain_trace_surface(rt_compute c, const float* origins, cons
 // query state (Shader::query, the claim counter) is the ray queries'; the constants' copy carries the query's eye.
 namespace {
 
-int shade_rays_enqueue(rt_compute c, const void* rays_device, int n, const rtq::SurfOptions& o, void* results_device,
-                       void* rgba8_device, void* steps_device)
+int shade_rays_enqueue(rt_compute c, const void* rays_device, uint32_t n, const rtq::SurfOptions& o,
+                       void* results_device, void* rgba8_device, void* steps_device)
 {
     rt_device dev = c->dev;
-    Shader* s = c->shader;
-    float eye[3];
-    if (int rc = sync_query_consts(dev, s, eye, (o.flags & rtq::kEye) ? o.eye : nullptr)) return rc;
-    if (o.flags & rtq::kEye) memcpy(eye, o.eye, sizeof(eye));
+    RtLaunch a;
+    RtShadeQuery q{};
+    if (int rc = query_prepare(c, o, true, &a, q.eye)) return rc;
     rtq::Plan p;
     const char* why = "";
-    if (int rc = rtq::plan_shade(n, o.flags, o.max_blocks, dev->num_cus - dev->reserve_cus, &p, &why))
+    if (int rc = rtq::plan_shade((int)n, o.flags, o.max_blocks, cus_of(dev), &p, &why))
         return fail(rc, "rt_terrain_shade_rays: %s", why);
-    RtLaunch a = make_launch(dev, s);
-    a.consts = s->query.d_consts;
-    a.grad = s->query.d_grad;
-    RtShadeQuery q{};
     q.rays = (const float4*)rays_device;
     q.results = (float4*)results_device;
     q.rgba8 = (uint32_t*)rgba8_device;
     q.steps = (uint32_t*)steps_device;
-    q.n = (uint32_t)n;
-    memcpy(q.eye, eye, sizeof(eye));
+    q.n = n;
     q.blocks = p.blocks;
-    q.t_min = o.t_min;
-    q.t_max = o.t_max;
-    q.stepmod = o.stepmod;
-    q.max_steps = rtq::surface_max_steps(o.max_steps);
-    q.ray_range = (o.flags & rtq::kSurfRayRange) != 0;
-    if (!dev->rq_counter) HIP_TRY(hipMalloc(&dev->rq_counter, 64));
-    HIP_TRY(hipMemsetAsync(dev->rq_counter, 0, 4, dev->stream));
-    q.counter = dev->rq_counter;
-    if (!rt_launch_shadequery(a, q)) return fail(RT_ERR_UNSUPPORTED, "rt_terrain_shade_rays: no kernel for this query");
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
+    q.march = march_params(o);
+    if (int rc = arm_counter(dev, &q.counter)) return rc;
+    return query_launched(rt_launch_shadequery(a, q), "rt_terrain_shade_rays: no kernel for this query");
 }
 
-// the checks both forms share, in the order the header gives; *o: the parsed options
-int shade_rays_check(rt_compute c, int n, const rt_surface_options* opt, rtq::SurfOptions* o)
+const QueryFamily<rtq::SurfOptions> kShadeFamily{"rt_terrain_shade_rays", "ray", rtq::parse_surface_options};
+
+// the shaded queries' clause
+auto shade_clause(rt_compute c)
 {
-    if (!c) return fail(RT_ERR_INVALID, "null compute");
-    const char* why = "";
-    if (int rc = rtq::check_count(n, &why)) return fail(rc, "rt_terrain_shade_rays: %s", why);
-    if (int rc = rtq::parse_surface_options(opt, o, &why)) return fail(rc, "rt_terrain_shade_rays: %s", why);
-    if (!c->shader) return fail(RT_ERR_STATE, "no current shader");
-    if (c->shader->kind != KIND_TRACESCREEN)
-        return fail(RT_ERR_INVALID, "rt_terrain_shade_rays: a camerarays compute has no SunDirection; pass the tracescreen compute");
-    if (o->flags & rtq::kForceSegments)
-        return fail(RT_ERR_UNSUPPORTED, "rt_terrain_shade_rays: shaded queries have no segment shape");
-    return RT_OK;
+    return [=](const rtq::SurfOptions& o, uint32_t*) -> int {
+        if (c->shader->kind != KIND_TRACESCREEN)
+            return fail(RT_ERR_INVALID,
+                        "rt_terrain_shade_rays: a camerarays compute has no SunDirection; pass the tracescreen compute");
+        if (o.flags & rtq::kForceSegments)
+            return fail(RT_ERR_UNSUPPORTED, "rt_terrain_shade_rays: shaded queries have no segment shape");
+        return RT_OK;
+    };
 }
 
 } // namespace
@@ -3064,56 +3099,34 @@ int shade_rays_check(rt_compute c, int n, const rt_surface_options* opt, rtq::Su
 extern "C" int rt_terrain_shade_rays_device(rt_compute c, const void* rays_device, int n, const rt_surface_options* opt,
                                             void* results_device, void* rgba8_device, void* steps_device)
 {
-    rtq::SurfOptions o;
-    if (int rc = shade_rays_check(c, n, opt, &o)) return rc;
-    if (n > 0 && !rays_device) return fail(RT_ERR_INVALID, "rt_terrain_shade_rays_device: null rays");
-    if (n > 0 && !results_device && !rgba8_device)
-        return fail(RT_ERR_INVALID, "rt_terrain_shade_rays_device: results and rgba8 are both null");
-    if (int rc = check_texture(c->shader)) return rc;
-    if (int rc = host_flag_check(c->dev)) return rc;
-    if (n == 0) return RT_OK;
-    HIP_TRY(hipSetDevice(c->dev->ordinal));
-    return shade_rays_enqueue(c, rays_device, n, o, results_device, rgba8_device, steps_device);
+    return query_entry(
+        c, kShadeFamily, n, opt, shade_clause(c),
+        !rays_device                       ? "rt_terrain_shade_rays_device: null rays"
+        : !results_device && !rgba8_device ? "rt_terrain_shade_rays_device: results and rgba8 are both null"
+                                           : nullptr,
+        [&](const rtq::SurfOptions& o, uint32_t nr) {
+            return shade_rays_enqueue(c, rays_device, nr, o, results_device, rgba8_device, steps_device);
+        });
 }
 
 extern "C" int rt_terrain_shade_rays(rt_compute c, const float* origins, const float* dirs, const float* ranges, int n,
                                      const rt_surface_options* opt, float* results, uint32_t* rgba8, uint32_t* steps)
 {
-    rtq::SurfOptions o;
-    if (int rc = shade_rays_check(c, n, opt, &o)) return rc;
-    if (n > 0 && (!origins || !dirs)) return fail(RT_ERR_INVALID, "rt_terrain_shade_rays: null origins or dirs");
-    if (n > 0 && !results && !rgba8) return fail(RT_ERR_INVALID, "rt_terrain_shade_rays: results and rgba8 are both null");
-    if (int rc = check_texture(c->shader)) return rc;
-    if (int rc = host_flag_check(c->dev)) return rc;
-    if (n == 0) return RT_OK;
-    // the host form packs the rays itself, so the spare words are the ranges exactly when it was given some
-    if (ranges) o.flags |= rtq::kSurfRayRange;
-    else o.flags &= ~rtq::kSurfRayRange;
-    rt_device dev = c->dev;
-    HIP_TRY(hipSetDevice(dev->ordinal));
-    // one device block: the packed rays, the results, the pixels, the step counts
-    const size_t nr = (size_t)n, rays_b = nr * 32, res_b = results ? nr * 32 : 0, px_b = rgba8 ? nr * 4 : 0,
-                 steps_b = steps ? nr * 8 : 0;
-    std::vector<float> packed(nr * 8);
-    rtq::pack(origins, dirs, n, packed.data());
-    if (ranges) rtq::pack_ranges(ranges, n, packed.data());
-    char* d = nullptr;
-    HIP_TRY(hipMalloc(&d, rays_b + res_b + px_b + steps_b));
-    char *d_res = d + rays_b, *d_px = d_res + res_b, *d_steps = d_px + px_b;
-    auto run = [&]() -> int {
-        HIP_TRY(hipMemcpyAsync(d, packed.data(), rays_b, hipMemcpyHostToDevice, dev->stream));
-        if (int rc = shade_rays_enqueue(c, d, n, o, results ? d_res : nullptr, rgba8 ? d_px : nullptr, steps ? d_steps : nullptr))
-            return rc;
-        if (results) HIP_TRY(hipMemcpyAsync(results, d_res, res_b, hipMemcpyDeviceToHost, dev->stream));
-        if (rgba8) HIP_TRY(hipMemcpyAsync(rgba8, d_px, px_b, hipMemcpyDeviceToHost, dev->stream));
-        if (steps) HIP_TRY(hipMemcpyAsync(steps, d_steps, steps_b, hipMemcpyDeviceToHost, dev->stream));
-        HIP_TRY(hipStreamSynchronize(dev->stream));
-        return RT_OK;
-    };
-    const int rc = run();
-    if (rc) (void)hipStreamSynchronize(dev->stream); // whatever was queued is over before the block is freed
-    (void)hipFree(d);
-    return rc;
+    return query_entry(
+        c, kShadeFamily, n, opt, shade_clause(c),
+        !origins || !dirs    ? "rt_terrain_shade_rays: null origins or dirs"
+        : !results && !rgba8 ? "rt_terrain_shade_rays: results and rgba8 are both null"
+                             : nullptr,
+        [&](rtq::SurfOptions o, uint32_t nr) {
+            const std::vector<float> packed = pack_surface_rays(origins, dirs, ranges, nr, &o);
+            // one device block: the packed rays, the results, the pixels, the step counts
+            const HostPart parts[] = {{nr * rtq::kRayBytes, packed.data(), nullptr},
+                                      {results ? nr * rtq::kSurfResultBytes : 0, nullptr, results},
+                                      {rgba8 ? nr * rtq::kPixelBytes : 0, nullptr, rgba8},
+                                      {steps ? nr * rtq::kShadeStepsBytes : 0, nullptr, steps}};
+            return host_form(c->dev, parts,
+                             [&](char* const* at) { return shade_rays_enqueue(c, at[0], nr, o, at[1], at[2], at[3]); });
+        });
 }
 
 // ---------------------------------------------------------------------------
@@ -3126,154 +3139,102 @@ int sample_field_enqueue(rt_compute c, const void* points_device, const rtq::Lat
                          const rtq::FieldOptions& o, void* results_device, void* occupancy_device)
 {
     rt_device dev = c->dev;
-    Shader* s = c->shader;
-    float eye[3];
-    if (int rc = sync_query_consts(dev, s, eye)) return rc;
-    if (o.flags & rtq::kEye) memcpy(eye, o.eye, sizeof(eye));
-    const int cus = dev->num_cus - dev->reserve_cus;
-    RtLaunch a = make_launch(dev, s);
-    a.consts = s->query.d_consts;
-    a.grad = s->query.d_grad;
+    RtLaunch a;
     RtFieldQuery q{};
+    if (int rc = query_prepare(c, o, false, &a, q.eye)) return rc;
     q.points = (const float4*)points_device;
     q.results = results_device;
     q.occupancy = (uint32_t*)occupancy_device;
     q.n = n;
-    memcpy(q.eye, eye, sizeof(eye));
     q.normal = (o.flags & rtq::kFieldNormal) != 0;
     rtq::FieldPlan p;
     if (lat) {
-        p = rtq::plan_field_lattice(lat->dims, s->landscape == RT_NOMADPLAINS, o.max_blocks, cus);
+        p = rtq::plan_field_lattice(lat->dims, a.landscape == RT_NOMADPLAINS, o.max_blocks, cus_of(dev));
         memcpy(q.origin, lat->origin, sizeof(q.origin));
         memcpy(q.spacing, lat->spacing, sizeof(q.spacing));
         memcpy(q.dims, lat->dims, sizeof(q.dims));
     } else {
-        p = rtq::plan_field_points(n, o.max_blocks, cus);
+        p = rtq::plan_field_points(n, o.max_blocks, cus_of(dev));
     }
     q.blocks = p.blocks;
     q.rows = p.rows;
     q.column = p.column;
-    if (!rt_launch_fieldquery(a, q)) return fail(RT_ERR_UNSUPPORTED, "field query: no kernel for this query");
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
+    return query_launched(rt_launch_fieldquery(a, q), "field query: no kernel for this query");
 }
 
-// the checks every form shares, in the order the header gives; *o: the parsed options
-int sample_field_check(rt_compute c, const rt_field_options* opt, rtq::FieldOptions* o, const char* who)
+// the two point entry points and the two lattice ones; their messages begin with the entry point's own name
+int sample_points_entry(const char* who, const char* missing, rt_compute c, const void* points, int n,
+                        const rt_field_options* opt, void* results, bool host)
 {
-    if (!c) return fail(RT_ERR_INVALID, "null compute");
-    const char* why = "";
-    if (int rc = rtq::parse_field_options(opt, o, &why)) return fail(rc, "%s: %s", who, why);
-    if (!c->shader) return fail(RT_ERR_STATE, "no current shader");
-    return RT_OK;
+    const QueryFamily<rtq::FieldOptions> f{who, "point", rtq::parse_field_options};
+    return query_entry(
+        c, f, n, opt, [](const rtq::FieldOptions&, uint32_t*) { return 0; }, !points || !results ? missing : nullptr,
+        [&](const rtq::FieldOptions& o, uint32_t np) {
+            if (!host) return sample_field_enqueue(c, points, nullptr, np, o, results, nullptr);
+            std::vector<float> packed((size_t)np * 4);
+            rtq::pack_points((const float*)points, n, packed.data());
+            // one device block: the packed points, the results
+            const HostPart parts[] = {{np * rtq::kPointBytes, packed.data(), nullptr},
+                                      {np * rtq::field_stride(o.flags), nullptr, results}};
+            return host_form(c->dev, parts, [&](char* const* at) {
+                return sample_field_enqueue(c, at[0], nullptr, np, o, at[1], nullptr);
+            });
+        });
 }
 
-int sample_lattice_check(rt_compute c, const rt_lattice* lat, const rt_field_options* opt, rtq::FieldOptions* o,
-                         rtq::Lattice* l, uint32_t* n, const void* results, const void* occupancy, const char* who)
+int sample_lattice_entry(const char* who, const char* both_null, rt_compute c, const rt_lattice* lat,
+                         const rt_field_options* opt, void* results, void* occupancy, bool host)
 {
-    if (int rc = sample_field_check(c, opt, o, who)) return rc;
-    const char* why = "";
-    if (int rc = rtq::check_lattice(lat, l, n, &why)) return fail(rc, "%s: %s", who, why);
-    if (*n > 0 && !results && !occupancy) return fail(RT_ERR_INVALID, "%s: results and occupancy are both null", who);
-    if (int rc = check_texture(c->shader)) return rc;
-    return host_flag_check(c->dev);
+    const QueryFamily<rtq::FieldOptions> f{who, nullptr, rtq::parse_field_options};
+    rtq::Lattice l;
+    return query_entry(
+        c, f, 0, opt,
+        [&](const rtq::FieldOptions&, uint32_t* n) -> int {
+            const char* why = "";
+            if (int rc = rtq::check_lattice(lat, &l, n, &why)) return fail(rc, "%s: %s", who, why);
+            return RT_OK;
+        },
+        !results && !occupancy ? both_null : nullptr,
+        [&](const rtq::FieldOptions& o, uint32_t n) {
+            if (!host) return sample_field_enqueue(c, nullptr, &l, n, o, results, occupancy);
+            // one device block: the results, the occupancy words
+            const HostPart parts[] = {{results ? n * rtq::field_stride(o.flags) : 0, nullptr, results},
+                                      {occupancy ? rtq::occupancy_bytes(l.dims) : 0, nullptr, occupancy}};
+            return host_form(c->dev, parts,
+                             [&](char* const* at) { return sample_field_enqueue(c, nullptr, &l, n, o, at[0], at[1]); });
+        });
 }
-
-// a field result's bytes per point
-size_t field_stride(const rtq::FieldOptions& o) { return (o.flags & rtq::kFieldNormal) ? 16 : 4; }
 
 } // namespace
 
 extern "C" int rt_terrain_sample_field_device(rt_compute c, const void* points_device, int n, const rt_field_options* opt,
                                               void* results_device)
 {
-    rtq::FieldOptions o;
-    const char* why = "";
-    if (!c) return fail(RT_ERR_INVALID, "null compute");
-    if (int rc = rtq::check_count(n, &why)) return fail(rc, "rt_terrain_sample_field_device: the point count must be 0..2^26");
-    if (int rc = sample_field_check(c, opt, &o, "rt_terrain_sample_field_device")) return rc;
-    if (n > 0 && (!points_device || !results_device))
-        return fail(RT_ERR_INVALID, "rt_terrain_sample_field_device: null points or results");
-    if (int rc = check_texture(c->shader)) return rc;
-    if (int rc = host_flag_check(c->dev)) return rc;
-    if (n == 0) return RT_OK;
-    HIP_TRY(hipSetDevice(c->dev->ordinal));
-    return sample_field_enqueue(c, points_device, nullptr, (uint32_t)n, o, results_device, nullptr);
+    return sample_points_entry("rt_terrain_sample_field_device", "rt_terrain_sample_field_device: null points or results",
+                               c, points_device, n, opt, results_device, false);
 }
 
 extern "C" int rt_terrain_sample_field(rt_compute c, const float* points, int n, const rt_field_options* opt,
                                        float* results)
 {
-    rtq::FieldOptions o;
-    const char* why = "";
-    if (!c) return fail(RT_ERR_INVALID, "null compute");
-    if (int rc = rtq::check_count(n, &why)) return fail(rc, "rt_terrain_sample_field: the point count must be 0..2^26");
-    if (int rc = sample_field_check(c, opt, &o, "rt_terrain_sample_field")) return rc;
-    if (n > 0 && (!points || !results)) return fail(RT_ERR_INVALID, "rt_terrain_sample_field: null points or results");
-    if (int rc = check_texture(c->shader)) return rc;
-    if (int rc = host_flag_check(c->dev)) return rc;
-    if (n == 0) return RT_OK;
-    rt_device dev = c->dev;
-    HIP_TRY(hipSetDevice(dev->ordinal));
-    // one device block: the packed points, the results
-    const size_t np = (size_t)n, pts_b = np * 16, res_b = np * field_stride(o);
-    std::vector<float> packed(np * 4);
-    rtq::pack_points(points, n, packed.data());
-    char* d = nullptr;
-    HIP_TRY(hipMalloc(&d, pts_b + res_b));
-    auto run = [&]() -> int {
-        HIP_TRY(hipMemcpyAsync(d, packed.data(), pts_b, hipMemcpyHostToDevice, dev->stream));
-        if (int rc = sample_field_enqueue(c, d, nullptr, (uint32_t)n, o, d + pts_b, nullptr)) return rc;
-        HIP_TRY(hipMemcpyAsync(results, d + pts_b, res_b, hipMemcpyDeviceToHost, dev->stream));
-        HIP_TRY(hipStreamSynchronize(dev->stream));
-        return RT_OK;
-    };
-    const int rc = run();
-    if (rc) (void)hipStreamSynchronize(dev->stream); // whatever was queued is over before the block is freed
-    (void)hipFree(d);
-    return rc;
+    return sample_points_entry("rt_terrain_sample_field", "rt_terrain_sample_field: null points or results", c, points,
+                               n, opt, results, true);
 }
 
 extern "C" int rt_terrain_sample_lattice_device(rt_compute c, const rt_lattice* lat, const rt_field_options* opt,
                                                 void* results_device, void* occupancy_device)
 {
-    rtq::FieldOptions o;
-    rtq::Lattice l;
-    uint32_t n = 0;
-    if (int rc = sample_lattice_check(c, lat, opt, &o, &l, &n, results_device, occupancy_device,
-                                      "rt_terrain_sample_lattice_device"))
-        return rc;
-    if (n == 0) return RT_OK;
-    HIP_TRY(hipSetDevice(c->dev->ordinal));
-    return sample_field_enqueue(c, nullptr, &l, n, o, results_device, occupancy_device);
+    return sample_lattice_entry("rt_terrain_sample_lattice_device",
+                                "rt_terrain_sample_lattice_device: results and occupancy are both null", c, lat, opt,
+                                results_device, occupancy_device, false);
 }
 
 extern "C" int rt_terrain_sample_lattice(rt_compute c, const rt_lattice* lat, const rt_field_options* opt, float* results,
                                          uint32_t* occupancy)
 {
-    rtq::FieldOptions o;
-    rtq::Lattice l;
-    uint32_t n = 0;
-    if (int rc = sample_lattice_check(c, lat, opt, &o, &l, &n, results, occupancy, "rt_terrain_sample_lattice")) return rc;
-    if (n == 0) return RT_OK;
-    rt_device dev = c->dev;
-    HIP_TRY(hipSetDevice(dev->ordinal));
-    // one device block: the results, the occupancy words (both 16-byte aligned: res_b is a multiple of 4 only)
-    const size_t res_b = results ? ((size_t)n * field_stride(o) + 15) / 16 * 16 : 0;
-    const size_t occ_b = occupancy ? (size_t)((l.dims[0] + 31u) / 32u) * l.dims[1] * l.dims[2] * 4 : 0;
-    char* d = nullptr;
-    HIP_TRY(hipMalloc(&d, res_b + occ_b));
-    auto run = [&]() -> int {
-        if (int rc = sample_field_enqueue(c, nullptr, &l, n, o, results ? d : nullptr, occupancy ? d + res_b : nullptr)) return rc;
-        if (results) HIP_TRY(hipMemcpyAsync(results, d, (size_t)n * field_stride(o), hipMemcpyDeviceToHost, dev->stream));
-        if (occupancy) HIP_TRY(hipMemcpyAsync(occupancy, d + res_b, occ_b, hipMemcpyDeviceToHost, dev->stream));
-        HIP_TRY(hipStreamSynchronize(dev->stream));
-        return RT_OK;
-    };
-    const int rc = run();
-    if (rc) (void)hipStreamSynchronize(dev->stream); // whatever was queued is over before the block is freed
-    (void)hipFree(d);
-    return rc;
+    return sample_lattice_entry("rt_terrain_sample_lattice",
+                                "rt_terrain_sample_lattice: results and occupancy are both null", c, lat, opt, results,
+                                occupancy, true);
 }
 
 // ---------------------------------------------------------------------------

@@ -128,3 +128,20 @@ def test_planning_header_under_sanitizers(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stdout.startswith("rayquery_check ok")
+
+
+def test_block_layout_and_option_prefix_under_sanitizers(tmp_path):
+    """tests/tools/querylayout_check.cpp: what the query families share in rt_rayquery.h -- the layout of the host
+    forms' device block (every part at a multiple of 16, in order, an absent part no space, size_t arithmetic at 2^26
+    elements, the largest lattice) and the one option-prefix parser behind the three option parsers (never past the
+    caller's size).  Its own main, its own process: nothing of it is loaded into this interpreter."""
+    cxx = shutil.which("g++")
+    assert cxx, "g++ is needed to build tests/tools/querylayout_check.cpp"
+    exe = str(tmp_path / "querylayout_check")
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan", "-I",
+                    os.path.join(ROOT, "gpgpuraytrace_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "tools", "querylayout_check.cpp"), "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.startswith("querylayout_check ok")
