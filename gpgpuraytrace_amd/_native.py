@@ -176,6 +176,7 @@ SIGNATURES = {
     "rt_varmgr_count": (_i, []),
     "rt_varmgr_register_compute": (_i, [_vp]),
     "rt_debug_math": (_i, [_vp, _i, _vp, _vp, _vp, _i]),
+    "rt_debug_sky_ceiling": (_i, [_vp, _i, C.c_float, _vp, _i, C.POINTER(C.c_double)]),
     "rt_debug_noise": (_i, [_vp, _vp, _vp, _i, _i]),
     "rt_debug_sky": (_i, [_vp, _vp, _vp, _i]),
 }

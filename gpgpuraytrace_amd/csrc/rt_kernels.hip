@@ -1162,6 +1162,9 @@ __global__ void __launch_bounds__(TraceThreads<L>::value) k_trace(const RtConsts
     if constexpr (STATS) c.nz.lds_calls = (__attribute__((address_space(3))) unsigned long long*)&s_st.v[BlockStats::NOISE];
     const uint32_t W = (uint32_t)k->width, H = (uint32_t)k->height, aa = (uint32_t)k->aa_samples;
     const int max_steps = k->max_steps;
+    // the primary march's sky exit (rt_shader.h sky_exit; rt_variants.h RT_SKY_EXIT): the product kernels only, the
+    // STATS kernels march every ray out (their step and noise counts are the oracle's)
+    constexpr bool kSky = RT_SKY_EXIT && L == RT_NOMADPLAINS && (!STATS || RT_SKY_EXIT_STATS);
     const uint32_t n_total = (uint32_t)__builtin_amdgcn_readfirstlane(m.n_units * m.n_frames); // units (an SGPR)
     // this block's hit stack and long-ray spill stack (hit_cap / long_spill_cap records per block)
     constexpr uint32_t HR = HitRec<L>::N;
@@ -1508,7 +1511,7 @@ __global__ void __launch_bounds__(TraceThreads<L>::value) k_trace(const RtConsts
     // march there with the density's octaves spread over the segment (density_nomadplains_seg,
     // bit-identical to density_nomadplains; pow_nonneg_wave for the step factor, bit-identical to
     // pow_nonneg) and come back when every segment's ray has left the march.
-    auto primary_seg = [&](const Ctx& cf, March<L, true>& st, bool lv, uint64_t lb, float spx, float spy) {
+    auto primary_seg = [&](const Ctx& cf, March<L, true>& st, bool lv, uint64_t lb, float spx, float spy, bool sky) {
         if constexpr (L == RT_NOMADPLAINS && kPrimarySeg > 0u && (!STATS || kStatsPrimarySeg)) {
             constexpr uint32_t LPR = 64u / (kPrimarySeg ? kPrimarySeg : 8u);
             const uint32_t lid = late(lane);
@@ -1537,6 +1540,9 @@ __global__ void __launch_bounds__(TraceThreads<L>::value) k_trace(const RtConsts
             const SegOctaves<LPR> g = seg_octaves<LPR>(cf, j);
             for (;;) {
                 if (live && !march_live<L, true, false>(cf, sg, RT_CAMERA_FAR, max_steps)) live = false;
+                if constexpr (kSky) { // (a segment's lanes hold one ray: they leave together)
+                    if (live && sky && sky_exit(sg.p.y, sg.dir.y, sg.dist)) live = false;
+                }
                 if (!__ballot(live)) break;
                 if (live) {
                     auto dens = [&](f3 q0) {
@@ -1927,6 +1933,8 @@ __global__ void __launch_bounds__(TraceThreads<L>::value) k_trace(const RtConsts
                 plane_x = gptr(ft->cells[f])[cell].x;
             }
         }
+        // the host vouches for the ceiling with these constants (read per unit: not held across the other loops)
+        [[maybe_unused]] const bool sky = kSky && k->sky_exit != 0;
         for (uint32_t a = 0; a < aa; ++a) {
             const uint32_t t = f * m.frame_samples + (u * 64u + lane) * aa + a;
             March<L, true> st;
@@ -1947,6 +1955,13 @@ __global__ void __launch_bounds__(TraceThreads<L>::value) k_trace(const RtConsts
             while (lv) {
                 lv = march_live<L, true, false>(cf, st, RT_CAMERA_FAR, max_steps);
                 if (!lv) break;
+                // a provable miss leaves before its next step (sky_exit, rt_shader.h): st.d <= 0 stays
+                if constexpr (kSky) {
+                    if (sky && sky_exit(st.p.y, st.dir.y, st.dist)) {
+                        lv = false;
+                        break;
+                    }
+                }
                 [[maybe_unused]] const uint64_t lb = __ballot(1); // the live rays
                 RT_DIAG_LIVE_HIST(if (lane == (uint32_t)__builtin_ctzll(lb)) atomicAdd(&g_live_hist[__popcll(lb)], 1ull);)
                 RT_DIAG_PRIMARY_STEPS({
@@ -1975,7 +1990,7 @@ __global__ void __launch_bounds__(TraceThreads<L>::value) k_trace(const RtConsts
             }
             if constexpr (L == RT_NOMADPLAINS && kPrimarySeg > 0u && (!STATS || kStatsPrimarySeg)) {
                 // the unit's last <= kPrimarySeg live rays finish on a segment of lanes each
-                if (const uint64_t lb = __ballot(lv)) primary_seg(cf, st, lv, lb, pxf + k->aa_off[a][0], pyf + k->aa_off[a][1]);
+                if (const uint64_t lb = __ballot(lv)) primary_seg(cf, st, lv, lb, pxf + k->aa_off[a][0], pyf + k->aa_off[a][1], sky);
             }
             __builtin_amdgcn_s_setprio(0);
             const bool hit = valid && st.d > 0.0f;
@@ -3216,6 +3231,10 @@ __global__ void k_debug_math(int op, const float* __restrict__ a, const float* _
             if (bn) atomicAdd(&cnt[1], (uint32_t)__popcll(bn));
             atomicAdd(&cnt[2], (uint32_t)__popcll(ba));
         }
+        return;
+    }
+    if (op == 14) { // k_trace's sky exit for the triple (p.y, dir.y, dist) at a[3 i]: 1 or 0
+        y[i] = rts::sky_exit(a[3 * i], a[3 * i + 1], a[3 * i + 2]) ? 1.0f : 0.0f;
         return;
     }
     float x = a[i], v = 0.0f;

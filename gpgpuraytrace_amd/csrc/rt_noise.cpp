@@ -87,4 +87,18 @@ void generate(uint32_t seed, int rand_kind, uint8_t* perm2d, float* grad)
     }
 }
 
+bool edge_gradients(const float* grad, int n)
+{
+    for (int i = 0; i < n; ++i) {
+        int nonzero = 0;
+        for (int a = 0; a < 3; ++a) {
+            const float g = grad[4 * i + a];
+            if (!(g == -1.0f || g == 0.0f || g == 1.0f)) return false;
+            nonzero += g != 0.0f;
+        }
+        if (nonzero > 2) return false;
+    }
+    return true;
+}
+
 } // namespace rt_noise

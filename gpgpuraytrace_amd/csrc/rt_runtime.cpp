@@ -515,6 +515,33 @@ void consts_sky_eye(RtConsts& k)
     k.sky_depth0 = rtm::exp(k.sky_sos * (200.0f - camHeight));
 }
 
+// nomadplains' FBM octave constants (pow(LUCAN, N) under R5) and exponent
+void consts_np_octaves(RtConsts& k)
+{
+    for (int n = 1; n <= RT_NP_OCTAVES; ++n) {
+        float S = rtm::pow(1.96f, (float)n);
+        k.np_scale[n] = S;
+        k.np_scale_y[n] = S * 0.35f;
+        k.np_rcp[n] = rtm::rcp(S);
+    }
+    k.np_expo = 0.68f + 0.1f;
+}
+
+// The nomadplains density's ceiling for a set of octave constants (rt_shader.h kSkyCeil has the argument):
+// C = pow(35 (1 + 30 B P), expo) (1 + 1e-3) in double, B = RT_NOISE_BOUND, P = the sum of the n_oct octave
+// weights in magnitude.  The kernel's literal RT_SKY_CEIL stands for it, so the sky exit is allowed
+// (the return value, RtConsts::sky_exit) only if C <= RT_SKY_CEIL, the exponent is one pow is monotone for, and
+// the gradient table (n_grad float4, may be null: not checked) holds what the bound B assumes.
+int sky_ceiling(const float* np_rcp, int n_oct, float expo, const float* grad, int n_grad, double* ceiling)
+{
+    double P = 0.0;
+    for (int n = 0; n < n_oct; ++n) P += std::fabs((double)np_rcp[n]);
+    const double C = std::pow(35.0 * (1.0 + 30.0 * (double)RT_NOISE_BOUND * P), (double)expo) * (1.0 + 1e-3);
+    if (ceiling) *ceiling = C;
+    const bool ok = expo > 0.0f && C <= (double)RT_SKY_CEIL && (!grad || rt_noise::edge_gradients(grad, n_grad));
+    return ok ? 1 : 0; // (a NaN in the constants fails the compares)
+}
+
 // Build the constant block from the cbuffer shadows (tracing.hlsl:6-41,
 // sky.hlsl:1-16/:74-80, landscape color constants, antialiasing.hlsl:9-49).
 void build_consts(const Shader& s, const rt_device_s& dev, RtConsts& k)
@@ -542,13 +569,16 @@ void build_consts(const Shader& s, const rt_device_s& dev, RtConsts& k)
     k.one_minus_step_factor = (float)(1.0 - (double)k.step_factor);
     k.density_factor = s.recording ? 0.15f : 0.35f;
     k.min_limit = (float)((double)0.02f * (double)0.03f);
-    for (int n = 1; n <= RT_NP_OCTAVES; ++n) {
-        float S = rtm::pow(1.96f, (float)n);
-        k.np_scale[n] = S;
-        k.np_scale_y[n] = S * 0.35f;
-        k.np_rcp[n] = rtm::rcp(S);
+    consts_np_octaves(k);
+    {
+        // k_trace's sky exit compares against the literal RT_SKY_CEIL: allowed only while these octave constants
+        // and the gradient table the launch will read keep the density's ceiling below it (249.7 here)
+        const auto& nz = s.cb[CB_NOISE];
+        float grad[128 * 4];
+        const bool has_grad = nz.size() >= sizeof(grad);
+        if (has_grad) memcpy(grad, nz.data(), sizeof(grad));
+        k.sky_exit = sky_ceiling(k.np_rcp + 1, RT_NP_OCTAVES, k.np_expo, has_grad ? grad : nullptr, 128, nullptr);
     }
-    k.np_expo = 0.68f + 0.1f;
     for (int n = 1; n <= RT_COL_OCTAVES; ++n) {
         float S = rtm::pow(2.03f, (float)n);
         k.col_scale[n] = S;
@@ -2692,6 +2722,13 @@ extern "C" int rt_terrain_set_target_depths(const float* cr, float* cells)
 }
 
 // ---- diagnostics ------------------------------------------------------------
+extern "C" int rt_debug_sky_ceiling(const float* np_rcp, int n_oct, float expo, const float* grad, int n_grad,
+                                    double* ceiling)
+{
+    if (!np_rcp || n_oct < 0 || (grad && n_grad < 0)) return fail(RT_ERR_INVALID, "bad arguments");
+    return sky_ceiling(np_rcp, n_oct, expo, grad, n_grad, ceiling);
+}
+
 extern "C" int rt_debug_math(rt_device d, int op, const float* a, const float* b, float* y, int n)
 {
     if (!d || !a || !y || n <= 0) return fail(RT_ERR_INVALID, "bad arguments");
@@ -2708,6 +2745,26 @@ extern "C" int rt_debug_math(rt_device d, int op, const float* a, const float* b
         HIP_TRY(hipMemcpy(y, dy, 12, hipMemcpyDeviceToHost));
         HIP_TRY(hipFree(da));
         HIP_TRY(hipFree(dy));
+        return RT_OK;
+    }
+    if (op == 14) {
+        // k_trace's sky exit predicate for n triples (p.y, dir.y, dist) at a[3 i]: out[i] = 1 or 0, and out[n] =
+        // the ceiling the host computed for the product's octave constants (rounded up to a float)
+        const size_t in = (size_t)n * 12, out = (size_t)n * 4;
+        HIP_TRY(hipMalloc(&da, in));
+        HIP_TRY(hipMalloc(&dy, out));
+        HIP_TRY(hipMemcpy(da, a, in, hipMemcpyHostToDevice));
+        rt_launch_debug_math(d->stream, op, da, da, dy, n);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(d->stream));
+        HIP_TRY(hipMemcpy(y, dy, out, hipMemcpyDeviceToHost));
+        HIP_TRY(hipFree(da));
+        HIP_TRY(hipFree(dy));
+        RtConsts k;
+        consts_np_octaves(k);
+        double C;
+        sky_ceiling(k.np_rcp + 1, RT_NP_OCTAVES, k.np_expo, nullptr, 0, &C);
+        y[n] = std::nextafter((float)C, INFINITY); // ((float)C may round down)
         return RT_OK;
     }
     size_t bytes = (size_t)n * 4;

@@ -461,6 +461,27 @@ __device__ __forceinline__ float density_nomadplains_column(const Ctx& c, f3 p, 
     return d + s;
 }
 
+// kNoiseBound >= max |noise3d|, for a gradient table of edge vectors (two components +-1, one 0: the host
+// checks the table it uploads, rt_noise.h edge_gradients).  noise3d blends the eight corner terms g_c . (f - c),
+// f in [0, 1]^3 the position in the cell and c in {0, 1}^3, with the fade weights w_c(f) = prod_a (u_a or
+// 1 - u_a), u = fade(f) in [0, 1]: non-negative and summing to 1, a convex combination.  An edge vector's dot
+// product picks two of the three |f_a - c_a| with signs, so |g_c . (f - c)| <= the sum of the two largest, and
+//     |noise3d| <= max_f sum_c w_c(f) (two largest |f_a - c_a|) = 1.0364
+// (scripts/noise_bound.py: a grid maximum; tests/test_sky_exit.py evaluates it on a grid whose Lipschitz slack
+// stays below 1.05 - max).  The float evaluation's rounding (relative 1e-6) is far inside the rest of 1.05.
+constexpr float kNoiseBound = RT_NOISE_BOUND;
+
+// kSkyCeil: nomadplains' density is negative wherever p.y > kSkyCeil.  d = -p.y + s (density_nomadplains):
+// s = pow(|30 fbm + 1| 35, expo) with |fbm| <= kNoiseBound P, P = the sum of the octave weights np_rcp[1..17]
+// (fewer octaves: a smaller sum); the terraces only subtract from s (-(t t) floorsize, floorsize = 1.8 steep
+// >= 0); the floor lift is fma(+0, 19, s) = s for 0.4 p.y >= 10.  So s <= C = pow(35 (1 + 30 kNoiseBound P),
+// expo) (1 + 1e-3): 249.7 for the product's constants; the 1e-3 covers the roundings of the 17 octave fmas,
+// of fma(s, 30, 1) * 35 (1e-6 together) and the few-ulp pow polynomials.  The host computes C in double from
+// the constants it uploads and sets RtConsts::sky_exit only if C <= kSkyCeil (rt_runtime.cpp sky_ceiling), so
+// the kernel compares against a literal.  With p.y > kSkyCeil >= s the exact sum -p.y + s is negative and
+// non-zero, and so is its rounding: d < 0.
+constexpr float kSkyCeil = RT_SKY_CEIL;
+
 #if RT_FBM_EXIT
 // (A/B build, rt_variants.h RT_FBM_EXIT) density_nomadplains with an exact early exit.  d = -y + F(s) + G
 // with F(s) = pow(|30 s + 1| 35, expo) and G (terraces + floor lift) independent of the FBM sum s.  After
@@ -470,7 +491,6 @@ __device__ __forceinline__ float density_nomadplains_column(const Ctx& c, f3 p, 
 // unit step whatever the exact d is (stepmult = 1 + pow(0, df) = 1), so the sample returns -2.5 in
 // place of d.  `allow` false (the march could exit after this sample) keeps the sample exact; the
 // exact path is density_nomadplains's operation sequence, bit for bit.
-constexpr float kNoiseBound = 1.05f; // grid maximum 1.0364 of sum_c w_c (two largest |f - c|), + slack
 // octaves from LDS table address op up to (not including) oe, as np_fbm's loop
 template <bool FAST>
 __device__ __forceinline__ float fbm_range(const Ctx& c, f3 q0, uint32_t op, uint32_t oe, float s)
@@ -845,6 +865,22 @@ __device__ __forceinline__ bool march_live(const Ctx& c, const March<L, CALCFOG>
 {
     if (SKIPREFINE && m.d > 0.0f) return false; // tracing.hlsl:84 `break` on a hit
     return m.dist < enddist && m.step > c.k->min_limit && !(max_steps > 0 && m.iters >= max_steps);
+}
+
+// The sky exit of k_trace's primary march (nomadplains, RT_SKY_EXIT), tested before a
+// step: the ray does not descend and its next sample, the one march_step_with would take, lies above kSkyCeil.
+// y(dist) = fma(dir_y, dist, p_y) is non-decreasing in dist for dir_y >= 0 (the exact value is, and rounding
+// keeps order).  The sample at y > kSkyCeil gives d < 0 (kSkyCeil, above), so the step adds lastStep > 0
+// (step > min_limit > 0, stepmult >= 1) to dist, the sample after it is no lower, and by induction no later
+// sample has d > 0: the ray never refines and ends a miss (d <= 0) by distance, step limit or max_steps.  A
+// fog-free miss pixel is the same bits wherever its march stopped (k_trace, miss_sample), so the ray may
+// leave here, with m.d the last evaluated sample's value (<= 0, or the initial 0): still a miss.
+// A refining ray cannot pass the test: d > 0 at its last sample, at distance D, means y(D) < s <= kSkyCeil
+// there, and the next sample is at D - lastStep <= D, so no higher.  -0 counts as not descending (y stays p_y);
+// a NaN in either operand fails a compare and the ray marches on.
+__device__ __forceinline__ bool sky_exit(float p_y, float dir_y, float dist)
+{
+    return dir_y >= 0.0f && fma(dir_y, dist, p_y) > kSkyCeil;
 }
 
 // march_live with skiprefine per lane (march_step_with's run-time skip)

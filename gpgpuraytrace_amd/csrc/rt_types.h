@@ -9,7 +9,9 @@ enum { RT_NOMADPLAINS = 0, RT_TESTING = 1, RT_SIMPLE = 2, RT_GREENROCKS = 3, RT_
 #define RT_CAMERA_NEAR 0.01f   // tracing.hlsl:3
 #define RT_CAMERA_FAR 5000.0f  // tracing.hlsl:4
 #define RT_NP_OCTAVES 17       // nomadplains FBM: detail = max(18 - dist^0.33, 2) with dist >= 0.01 -> N <= 17
-#define RT_COL_OCTAVES 20      // nomadplains colour FBM (color.hlsl:31); simple's dynamic one stays below 16
+#define RT_NOISE_BOUND 1.05f   // >= max |noise3d| for edge-vector gradients (rt_shader.h kNoiseBound)
+#define RT_SKY_CEIL 256.0f     // nomadplains: density < 0 wherever y > RT_SKY_CEIL (rt_shader.h sky_exit)
+#define RT_COL_OCTAVES 20     // nomadplains colour FBM (color.hlsl:31); simple's dynamic one stays below 16
 
 // Per-frame constant block.  Built on the host from the cbuffer shadows the
 // engine writes through IShaderVariable::write (CBFrame, CBPermanent,
@@ -46,7 +48,10 @@ struct RtConsts {
     int32_t max_steps; // build extension (0 = unbounded, reference semantics)
     int32_t ao_samples; // build extension: AO rays per primary hit (0 = off, reference semantics)
     int32_t width, height;
-    int32_t pad[3];
+    // 1: these constants keep the nomadplains density below kSkyCeil above y = kSkyCeil (the host's proof
+    // obligation, rt_runtime.cpp sky_ceiling), so k_trace may end such rays early; 0: it marches them out
+    int32_t sky_exit;
+    int32_t pad[2];
 };
 
 // Frame-level statistics written by the instrumented kernels.

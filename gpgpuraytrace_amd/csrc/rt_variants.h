@@ -184,6 +184,19 @@
 #define RT_FBM_EXIT 0
 #endif
 
+// RT_SKY_EXIT: the product k_trace (nomadplains, not the STATS kernels) ends a primary ray whose direction
+// does not descend once its next sample lies above the terrain's ceiling kSkyCeil (rt_shader.h sky_exit;
+// DESIGN.md section 2, rule R10): the ray is a miss whatever the rest of its march does, and a fog-free miss
+// pixel does not depend on where the march stops.  0: every ray marches to its end (the A/B).
+// RT_SKY_EXIT_STATS=1 (diagnostic builds only) gives the STATS kernels the exit too, so their primary_steps and
+// noise_calls count what the product executes instead of what the oracle does (profiles/r10/sky_exit.md).
+#ifndef RT_SKY_EXIT
+#define RT_SKY_EXIT 1
+#endif
+#ifndef RT_SKY_EXIT_STATS
+#define RT_SKY_EXIT_STATS 0
+#endif
+
 // A/B overrides of the field queries' lattice plan (rt_rayquery.h plan_field_lattice; scripts/field_query_bench.py):
 // RT_FIELD_ROWS > 0 replaces the plan's iy rows per strip, RT_FIELD_COLUMN 0 switches nomadplains' column reuse
 // off.  The results are the same bits either way.  profiles/r12/field_query.md.

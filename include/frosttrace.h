@@ -617,11 +617,20 @@ int rt_terrain_sample_lattice_device(rt_compute cs, const rt_lattice* lat, const
  *   op 12 sweeps the nomadplains octave-count estimate over the n floats whose bit
  *   patterns follow bits(a[0]) and writes 3 uint32 to out: unflagged estimates that differ
  *   from the exact count, flagged estimates, patterns swept.
+ *   op 14 evaluates the trace kernel's sky-exit predicate (a primary ray that does not descend and whose
+ *   next sample lies above the nomadplains ceiling, 256) for n triples (p.y, dir.y, dist) at a[3 i] (a: 3 n
+ *   floats, b unused): out[i] = 1 or 0, and out[n] (out: n + 1 floats) = the ceiling the host computed for
+ *   the product's octave constants, which must not exceed 256.
+ * rt_debug_sky_ceiling (host only, no device): the nomadplains density's ceiling for n_oct octave weights
+ *   np_rcp[0 .. n_oct) and the pow exponent, in double to *ceiling (may be NULL); returns 1 if the host
+ *   would allow the sky exit with them (ceiling <= 256, and the n_grad float4 gradients at grad, if not
+ *   NULL, are all edge vectors), 0 if it would switch the exit off, < 0 for bad arguments.
  * rt_debug_noise: noise3d (density = 0, noise.hlsl:153-179) or the compute's landscape
  *   getDensity (density = 1) at n points (xyz interleaved), with the compute's
  *   current tables and constants; density = 2: nomadplains' steep noise noise3d(x, y, 0)
  *   (z ignored), 3: its short-integer-path variant (|x|, |y| < 8192). */
 int rt_debug_math(rt_device dev, int op, const float* a, const float* b, float* out, int n);
+int rt_debug_sky_ceiling(const float* np_rcp, int n_oct, float expo, const float* grad, int n_grad, double* ceiling);
 int rt_debug_noise(rt_compute cs, const float* xyz, float* out, int n, int density);
 /* rt_debug_sky (ABI 4): the sky of n view directions (xyz interleaved) with the compute's current
  *   constants (Eye, SunDirection) and tables: 7 floats per direction, getRayleighMieColor's
