@@ -30,8 +30,9 @@ namespace {
 // LDS image (rts::NoiseView): perm2D texels at offset 0 (64 KiB), the paired lane-private
 // gradients gxy at kLdsGxy (32 KiB) and gz at kLdsGz (32 KiB, 8 of every 16 B used), then the
 // nomadplains FBM octave constants (NoiseView::oct): (S, 0.35 S, 1/S, 0) for N = 0..RT_NP_OCTAVES + 2
-// (the entries past the last octave are padding).  A kernel declares it as its ONLY static LDS array, so it sits
-// at LDS address 0 and the texel address needs no base (other LDS a kernel needs is carved after it).
+// (.w is unused and stays 0; the entries past the last octave are padding).  A kernel declares it as its
+// ONLY static LDS array, so it sits at LDS address 0 and the texel address needs no base (other LDS a
+// kernel needs is carved after it).
 constexpr int kPermWords = 128 * 128;
 constexpr int kNpOct = RT_NP_OCTAVES + 3;
 constexpr int kOctWords = kNpOct * 4;
@@ -48,11 +49,7 @@ __device__ __forceinline__ void load_noise_lds(uint32_t* lds, const uint32_t* __
         const int i = threadIdx.x;
         if (i < kNpOct) {
             const int n = i <= RT_NP_OCTAVES ? i : RT_NP_OCTAVES;
-            float pre = 0.0f; // RT_FBM_EXIT: sum of the octave weights 1 .. n (the suffix bound's prefix)
-#if RT_FBM_EXIT
-            for (int m = 1; m <= n; ++m) pre += k->np_rcp[m];
-#endif
-            oct[i] = make_float4(k->np_scale[n], k->np_scale_y[n], k->np_rcp[n], pre);
+            oct[i] = make_float4(k->np_scale[n], k->np_scale_y[n], k->np_rcp[n], 0.0f);
         }
     }
     float4* gxy = reinterpret_cast<float4*>(lds + kLdsGxy / 4);
@@ -298,8 +295,8 @@ struct UnitMap {
     uint32_t order_batch; // k_order: 1 one longest-first order over the batch, 0 one per frame (frame-major)
     uint32_t cells_from_cam; // k_order first derives each frame's CellDistance from its CameraResults
     // 1: one sample per pixel, no float output, <= 1 AO ray per hit: hit pixels are finished in k_trace
-    // where their last ray ends (fit_pixel), and k_finish only finishes the hits whose long shadow and
-    // AO ray race (their bit in hitmask); with no AO, no k_finish at all
+    // where their last ray ends (fit_pixel), and k_finish only finishes the hits that have a long shadow
+    // beside their AO ray (their bit in hitmask); with no AO, no k_finish at all
     uint32_t fit;
     // 1: one sample per pixel, no float output, >= 2 AO rays per hit: a hit whose shadow ends at its first
     // step (no long shadow) keeps its colour in its block's colour pool beside its AO counter slot, and the
@@ -648,27 +645,6 @@ __device__ __forceinline__ void ao_count(uint32_t* __restrict__ aocc, uint32_t t
 }
 // UnitMap::fitm with AO: a sample k_finish finishes carries kFinFlag in its byte (plain stores, k_trace)
 constexpr uint32_t kFinFlag = 0x80u;
-// UnitMap::fit with its one AO ray per hit: a hit whose shadow ray outlived its first step has two rays left,
-// the long shadow S and the AO ray A, and whichever ends second stores the pixel (no k_finish).  Each ends
-// with one device atomic OR on the sample's aocc byte -- kRaceS, or kRaceA | occluded -- and the one whose OR
-// returns the other's bit is second.  S stores its colour (samples) and waits for it before its OR, so a
-// second A reads it from the L2 with sc1; both rays of a hit are one block's (one CU, one L2).  The second
-// clears the byte for the next launch.  k_finish's arithmetic (fit_pixel), so the same bits.
-constexpr uint32_t kRaceS = 0x40u, kRaceA = 0x20u;
-__device__ __forceinline__ uint32_t race_or(uint32_t* __restrict__ aocc, uint32_t t, uint32_t bits)
-{
-    const uint32_t sh = (t & 3u) * 8u;
-    return (atomicOr(&aocc[late(t) >> 2], bits << sh) >> sh) & 0xffu;
-}
-// a hit's 12-byte colour record (sample_store, one sample per pixel), written by another wave: sc1, waited
-__device__ __forceinline__ float4 ld_colour_fresh(const float4* samples, uint32_t t)
-{
-    typedef float v3f __attribute__((ext_vector_type(3)));
-    const float* p = reinterpret_cast<const float*>(samples) + 3u * late(t);
-    v3f v;
-    asm volatile("global_load_dwordx3 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(p) : "memory");
-    return make_float4(v.x, v.y, v.z, 1.0f);
-}
 __device__ __forceinline__ uint32_t ao_occluded(const uint32_t* __restrict__ aocc, uint32_t t)
 {
     return (aocc[t >> 2] >> ((t & 3u) * 8u)) & 0x7fu;
@@ -859,37 +835,6 @@ __device__ __forceinline__ void ao_begin(const Ctx& c, const ShadeHit& h, uint32
     march_begin(c, st, h.hp, 0.4f, h.prec, ao_dir(h.n, h.px, h.py, h.a, kk), false);
 }
 
-// AO generator record (RT_AO_GEN, AO_SAMPLES >= 2): a shaded hit's AO rays as ONE ring record, expanded
-// into its AO_SAMPLES rays at refill, one lane each (gen_begin), instead of AO_SAMPLES long-ray records
-// pushed by the shading (64 hits x (1 + AO_SAMPLES) records per batch overflowed the LDS ring into the
-// spill stack: C5's long-ray spills).  (hit position, stepmod), (n.x, aux, kGenMark, t),
-// (n.y, n.z, px | py << 16, a): kGenMark in a long record's iters slot (a march has far fewer steps).
-constexpr uint32_t kGenMark = 0xfffffff0u;
-// generator records carry 2 .. 8 AO rays: a post-drain segment wave (8 rays) must be able to take one whole
-__device__ __forceinline__ bool gen_on(const RtConsts* k)
-{
-    return RT_AO_GEN && k->ao_samples >= 2 && k->ao_samples <= 8 && 64u / (RT_SEG_LANES ? RT_SEG_LANES : 8u) >= 8u;
-}
-__device__ __forceinline__ bool rec_is_gen(float4 r1) { return __float_as_uint(r1.z) == kGenMark; }
-__device__ __forceinline__ void gen_pack(const ShadeHit& h, uint32_t t, uint32_t aux, float4* r)
-{
-    r[0] = make_float4(h.hp.x, h.hp.y, h.hp.z, h.prec);
-    r[1] = make_float4(h.n.x, __uint_as_float(aux), __uint_as_float(kGenMark), __uint_as_float(t));
-    r[2] = make_float4(h.n.y, h.n.z, __uint_as_float(h.px | (h.py << 16)), __uint_as_float(h.a));
-}
-// AO ray kk of a generator record: ao_begin's march state (the state long_pack + long_unpack would
-// carry: lastStep, d, f and sd are not read before the first step overwrites them)
-template <int L>
-__device__ __forceinline__ uint32_t gen_begin(const Ctx& c, float4 r0, float4 r1, float4 r2, uint32_t kk,
-                                              March<L, true>& st, uint32_t* aux)
-{
-    *aux = __float_as_uint(r1.y);
-    const uint32_t pp = __float_as_uint(r2.z);
-    march_begin(c, st, rtm::mk(r0.x, r0.y, r0.z), 0.4f, r0.w,
-                ao_dir(rtm::mk(r1.x, r2.x, r2.y), pp & 0xffffu, pp >> 16, __float_as_uint(r2.w), kk), false);
-    return __float_as_uint(r1.w);
-}
-
 // The inputs a long shadow ray needs to finish its sample: (albedo + specular, brightness), fcolord
 // (fog-live landscapes only; 0 otherwise) and (rayleigh, skyAmount): FinRec<L>::N float4 at f, a
 // slot of the block's fin pool or fin[t].
@@ -943,18 +888,10 @@ __device__ __forceinline__ void long_finish(const RtConsts* k, const UnitMap& m,
                                             uint32_t aux, const March<L, true>& st)
 {
     if (aux_ao(aux)) {
-        if (RT_FIT_RACE && m.fit && aux == kAuxAO) { // fit: the AO ray of a hit with a long shadow races it (kRaceS)
-            const uint32_t occ = st.d > 0.0f ? 1u : 0u;
-            if (race_or(aocc, t, kRaceA | occ) & kRaceS) { // second: the shadow's colour is in
-                if (!(RT_DIAG_SKIP & 2)) fit_store(k, m, fr, t, fit_pixel(ld_colour_fresh(samples, t), ao_factor(occ, 1)));
-                reinterpret_cast<uint8_t*>(aocc)[late(t)] = 0u;
-            }
-            return;
-        }
         if (st.d > 0.0f) {
             if (aux == kAuxAO) {
-                // (RT_FIT_RACE 0) fit: the hit's one AO ray, after the shading's kFinFlag store (ordered by the push)
-                if (!RT_FIT_RACE && m.fit) reinterpret_cast<uint8_t*>(aocc)[late(t)] = (uint8_t)(kFinFlag | 1u);
+                // fit: the hit's one AO ray, after the shading's kFinFlag store (ordered by the push)
+                if (m.fit) reinterpret_cast<uint8_t*>(aocc)[late(t)] = (uint8_t)(kFinFlag | 1u);
                 // one AO ray per hit: its count has one writer, a plain byte store (no device atomic)
                 else if (k->ao_samples == 1) reinterpret_cast<uint8_t*>(aocc)[late(t)] = 1u;
                 else if (!(RT_DIAG_SKIP & 8)) ao_count(aocc, t);
@@ -978,14 +915,6 @@ __device__ __forceinline__ void long_finish(const RtConsts* k, const UnitMap& m,
         const float4 v = shade_finish(k, f0, fog, f1, st.d, st.f.w);
         if (m.fit && k->ao_samples == 0) {
             if (!(RT_DIAG_SKIP & 2)) fit_store(k, m, fr, t, fit_pixel(v, 1.0f));
-        } else if (RT_FIT_RACE && m.fit) { // its AO ray races it (kRaceA): the colour first, in L2 before the OR
-            sample_store(k, samples, t, v);
-            __builtin_amdgcn_s_waitcnt(0);
-            const uint32_t ob = race_or(aocc, t, kRaceS);
-            if (ob & kRaceA) { // second
-                if (!(RT_DIAG_SKIP & 2)) fit_store(k, m, fr, t, fit_pixel(v, ao_factor(ob & 1u, 1)));
-                reinterpret_cast<uint8_t*>(aocc)[late(t)] = 0u;
-            }
         } else if (!(RT_DIAG_SKIP & 4)) {
             sample_store(k, samples, t, v);
         }
@@ -1213,60 +1142,6 @@ __global__ void __launch_bounds__(TraceThreads<L>::value) k_trace(const RtConsts
         push_recs(want, [&](float4* r) { long_pack(st, t, aux, r); });
     };
 
-#if RT_AO_GEN
-    // Refill (the lock held; RT_AO_GEN with AO generator records): fill up to nslots ray slots from the
-    // ring (from its head) and then the spill stack (from its top), whole records only, a generator
-    // record filling AO_SAMPLES consecutive slots.  Candidate record i is lane i's; slot `slot` (want)
-    // finds its record by a binary search over the records' first slots.  Sets the slot's ray; returns
-    // the records taken from the ring (take) and the spill stack (more).
-    auto refill_gen = [&](uint32_t head, uint32_t tail, uint32_t sl, uint32_t nslots, uint32_t slot, bool want,
-                          March<L, true>& st, uint32_t& t, uint32_t& aux, bool& live, Ctx& cl, uint32_t* more_out) {
-        const uint32_t A = (uint32_t)k->ao_samples, avail = tail - head;
-        const uint32_t ci = late(lane);
-        const bool cand = ci < avail + sl && ci < nslots; // (a record takes at least one slot)
-        float4 r1 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (cand) r1 = ci < avail ? q.longs[((head + ci) % kLongRing) * kShadowRec + 1u]
-                                  : ld_rec(lspill, (sl - 1u - (ci - avail)) * kShadowRec + 1u);
-        const uint64_t gb = __ballot(cand && rec_is_gen(r1));
-        const uint32_t gens_before = lane_rank(gb);
-        const uint32_t start = ci + (A - 1u) * gens_before; // first slot of candidate ci
-        const uint32_t cnt = ((gb >> ci) & 1ull) ? A : 1u;
-        const uint64_t tb = __ballot(cand && start + cnt <= nslots);
-        const uint32_t ncand = (uint32_t)__popcll(tb); // whole records that fit (a prefix of the candidates)
-        const uint32_t take = ncand < avail ? ncand : avail;
-        *more_out = ncand - take;
-        uint32_t cc = 0;
-        for (uint32_t step = 32u; step != 0u; step >>= 1u) {
-            const uint32_t nx = cc + step;
-            const uint32_t s2 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((nx & 63u) << 2), (int)start);
-            if (nx < ncand && s2 <= slot) cc = nx;
-        }
-        const uint32_t kk = slot - (uint32_t)__builtin_amdgcn_ds_bpermute((int)(cc << 2), (int)start);
-        const uint32_t ncc = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(cc << 2), (int)cnt); // slots of record cc
-        if (want && cc < ncand && kk < ncc) { // (slots past the last whole record stay empty)
-            float4 q0, q1, q2;
-            if (cc < avail) {
-                const float4* r = &q.longs[((head + cc) % kLongRing) * kShadowRec];
-                q0 = r[0];
-                q1 = r[1];
-                q2 = r[2];
-            } else {
-                const uint32_t ri = (sl - 1u - (cc - avail)) * kShadowRec;
-                q0 = ld_rec(lspill, ri);
-                q1 = ld_rec(lspill, ri + 1u);
-                q2 = ld_rec(lspill, ri + 2u);
-            }
-            if (rec_is_gen(q1)) t = gen_begin<L>(c, q0, q1, q2, kk, st, &aux);
-            else t = long_unpack(q0, q1, q2, rtm::mk(0.0f, 0.0f, 0.0f), st, &aux);
-            const float* fr = s_fr.v[frame_of(m, t)];
-            cl.eye = rtm::mk(fr[0], fr[1], fr[2]);
-            if (!aux_ao(aux)) st.dir = rtm::mk(fr[3], fr[4], fr[5]);
-            live = true;
-        }
-        return take;
-    };
-#endif
-
     // the fin pool slots of finished shadow rays (idle lanes whose aux is a slot) go back to the free
     // list; the lock is held
     auto free_fin_locked = [&](bool live, uint32_t& aux) {
@@ -1315,11 +1190,6 @@ __global__ void __launch_bounds__(TraceThreads<L>::value) k_trace(const RtConsts
         }
     };
 
-    // RT_SEG_DRAIN_ALL: after the drain every long ray goes to the segment waves (nomadplains only: the other
-    // landscapes have no segment march, so their waves keep refilling)
-    // (2: no refill after the drain, but a wave keeps the rays it holds: new rays go to segment waves only)
-    constexpr bool kSegDrainAll = RT_SEG_DRAIN_ALL != 0 && L == RT_NOMADPLAINS && kSegLanes > 0u;
-    constexpr bool kSegDrainHandAll = RT_SEG_DRAIN_ALL == 1 && kSegDrainAll;
     // ---- a batch of long rays, lane refill from the ring ----
     auto do_shadow = [&]() {
         March<L, true> st;
@@ -1339,26 +1209,10 @@ __global__ void __launch_bounds__(TraceThreads<L>::value) k_trace(const RtConsts
             }
             const uint64_t idle = __ballot(!live);
             const uint32_t nidle = (uint32_t)__popcll(idle);
-            if (nidle >= refill_idle && queued_long() != 0u && !(kSegDrainAll && vload(q.drained) != 0u)) {
+            if (nidle >= refill_idle && queued_long() != 0u) {
                 q_lock(&q.lock, lane);
                 free_fin_locked(live, aux);
                 const uint32_t head = vload(q.l_head), tail = vload(q.l_tail);
-#if RT_AO_GEN
-                if (gen_on(k)) { // AO generator records: whole records into the idle lanes
-                    const uint32_t sl = vload(q.ls_top);
-                    uint32_t more;
-                    const bool idl = (idle >> lane) & 1ull;
-                    const uint32_t take = refill_gen(head, tail, sl, nidle, lane_rank(idle), idl, st, t, aux, live, cl, &more);
-                    if (more) __builtin_amdgcn_s_waitcnt(0);
-                    if (lane == 0) {
-                        q.l_head = head + take;
-                        q.ls_top = sl - more;
-                    }
-                    q_unlock(&q.lock, lane);
-                    goto refilled;
-                }
-#endif
-                {
                 const uint32_t take = (tail - head) < nidle ? (tail - head) : nidle;
                 // the block's spill stack tops up what the LDS ring cannot give (from its top)
                 const uint32_t sl = vload(q.ls_top);
@@ -1385,11 +1239,7 @@ __global__ void __launch_bounds__(TraceThreads<L>::value) k_trace(const RtConsts
                     q.ls_top = sl - more;
                 }
                 q_unlock(&q.lock, lane);
-                }
             }
-#if RT_AO_GEN
-            refilled:
-#endif
             const uint64_t lv = __ballot(live);
             // The ring ran dry and few lanes are left: rather than march them on
             // mostly empty lanes, hand them back to the ring (another wave will merge
@@ -1397,8 +1247,8 @@ __global__ void __launch_bounds__(TraceThreads<L>::value) k_trace(const RtConsts
             const bool drained_now = vload(q.drained) != 0u;
             bool hand_back = lv != 0ull && (uint32_t)__popcll(lv) < compact_live && queued_long() == 0u && !drained_now;
             if constexpr (L == RT_NOMADPLAINS && kSegLanes > 0u) // after the drain: few rays go to segment waves
-                hand_back = hand_back || (drained_now && lv != 0ull && (kSegDrainHandAll ||
-                                          ((uint32_t)__popcll(lv) <= kSegHandBack && queued_long() == 0u)));
+                hand_back = hand_back || (drained_now && lv != 0ull && (uint32_t)__popcll(lv) <= kSegHandBack &&
+                                          queued_long() == 0u);
             if (lv == 0ull || hand_back) {
                 if (__ballot(!live && (aux < kFinSlots || aux_slot_free(aux)))) {
                     q_lock(&q.lock, lane);
@@ -1434,14 +1284,9 @@ __global__ void __launch_bounds__(TraceThreads<L>::value) k_trace(const RtConsts
             cl.nz.phase = RT_PHASE_LONG;
             q_lock(&q.lock, lane);
             const uint32_t head = vload(q.l_head), tail = vload(q.l_tail);
-            uint32_t take = (tail - head) < RPW ? (tail - head) : RPW;
+            const uint32_t take = (tail - head) < RPW ? (tail - head) : RPW;
             const uint32_t sl = vload(q.ls_top);
-            uint32_t more = sl < RPW - take ? sl : RPW - take;
-#if RT_AO_GEN
-            if (gen_on(k)) { // AO generator records: whole records into the segments
-                take = refill_gen(head, tail, sl, RPW, late(lane) / LPR, true, st, t, aux, live, cl, &more);
-            } else
-#endif
+            const uint32_t more = sl < RPW - take ? sl : RPW - take;
             if (const uint32_t grp = late(lane) / LPR; grp < take + more) { // every lane of the segment unpacks the same record
                 float4 r0, r1, r2;
                 if (grp < take) {
@@ -1660,10 +1505,10 @@ __global__ void __launch_bounds__(TraceThreads<L>::value) k_trace(const RtConsts
         // are k_finish's.  Plain stores, no atomics (a device-scope atomic costs a 32-B HBM write on gfx950,
         // L2 or not: scripts/ubench_atomic.hip): the sample's aocc byte becomes kFinFlag and the unit's
         // hitmask word, zero from the unit, becomes nonzero (every writer stores the same value); a long
-        // shadow's slot marks it (bit 10: its completion stores the flagged count).  (fit: no k_finish; a long
-        // shadow and its AO ray race in long_finish, kRaceS / kRaceA)
-        const bool kfin = valid && ((!RT_FIT_RACE && m.fit && k->ao_samples && more) ||
-                                    (m.fitm && (more || !aux_ao_slot(ao_aux)))); // (fit: the race, long_finish)
+        // shadow's slot marks it (bit 10: its completion stores the flagged count).  fit with its one AO ray: the
+        // hits with a long shadow are k_finish's in the same way (their AO ray adds its count to the flag,
+        // long_finish)
+        const bool kfin = valid && ((m.fit && k->ao_samples && more) || (m.fitm && (more || !aux_ao_slot(ao_aux))));
         if (kfin) {
             reinterpret_cast<uint8_t*>(aocc)[late(t)] = (uint8_t)kFinFlag;
             hitmask[t >> 6] = 1ull;
@@ -1677,11 +1522,6 @@ __global__ void __launch_bounds__(TraceThreads<L>::value) k_trace(const RtConsts
         // AO extension: the hit's AO rays start as long rays (fit: after its unoccluded pixel is stored,
         // which an occluded AO ray overwrites)
         if (m.fit || m.fitm) __builtin_amdgcn_s_waitcnt(0);
-#if RT_AO_GEN
-        if (gen_on(k)) { // one generator record per hit (expanded at refill)
-            push_recs(valid, [&](float4* r) { gen_pack(h, t, ao_aux, r); });
-        } else
-#endif
         for (int kk = 0; kk < k->ao_samples; ++kk) {
             March<L, true> ao;
             if (valid) ao_begin(c, h, (uint32_t)kk, ao);
@@ -1973,15 +1813,6 @@ __global__ void __launch_bounds__(TraceThreads<L>::value) k_trace(const RtConsts
                 if constexpr (L == RT_NOMADPLAINS && kPrimarySeg > 0u && (!STATS || kStatsPrimarySeg)) {
                     if ((uint32_t)__popcll(lb) <= kPrimarySeg) break;
                 }
-#if RT_FBM_EXIT
-                if constexpr (L == RT_NOMADPLAINS) {
-                    // exact unless the march provably continues after this sample (RT_FBM_EXIT)
-                    const float ns = st.step * k->step_factor;
-                    const bool allow = st.dist + ns < RT_CAMERA_FAR && ns > k->min_limit &&
-                                       !(max_steps > 0 && st.iters + 1 >= max_steps);
-                    march_step_with<L, true, false>(cf, st, [&](f3 q) { return density_nomadplains_x(cf, q, allow); });
-                } else
-#endif
                 march_step<L, true, false>(cf, st);
                 if (it == 96u) __builtin_amdgcn_s_setprio(1);
                 else if (it == 224u) __builtin_amdgcn_s_setprio(2);
@@ -2051,9 +1882,6 @@ __global__ void __launch_bounds__(TraceThreads<L>::value) k_trace(const RtConsts
     bool first_unit = true;
     bool np_open = np.tasks != 0u; // the next batch's prepass tasks may remain (FusedPrepass)
     bool gp_open = GATED && gp.tasks != 0u; // this batch's own prepass tasks may remain (GatedPrepass)
-#if RT_GATE_STATIC
-    uint32_t gp_next = first_qi;
-#endif
     if constexpr (GATED) {
         if (gp.debug & 1u) { // RT_DEVICE_DEBUG_GATE_STRESS: this CU's L1 holds the frames' previous CellDistance
             float acc = 0.0f;
@@ -2068,15 +1896,7 @@ __global__ void __launch_bounds__(TraceThreads<L>::value) k_trace(const RtConsts
             // the gated launch: this batch's own prepass before anything else (every unit waits for some
             // of its rays).  Tasks are taken by resident waves, so every taken task finishes.
             if (GATED && gp_open) {
-#if RT_GATE_STATIC
-                // static: the wave's tasks are its first-unit index and every n_static-th after it, so the
-                // first ones go to wave 0 of each block in the order the blocks start, then wave 1, ...: one
-                // task wave per SIMD (the standalone prepass's shape) instead of the first blocks' 16 waves
-                const uint32_t qt = gp_next;
-                gp_next += n_static;
-#else
                 const uint32_t qt = wave_fetch(&counters[RT_CTR_GATE], lane);
-#endif
                 if (qt < gp.tasks * kPrepassSplit) {
                     WT(const unsigned long long tp = __builtin_amdgcn_s_memrealtime();)
                     do_prepass(ft, qt, true);
@@ -2105,10 +1925,8 @@ __global__ void __launch_bounds__(TraceThreads<L>::value) k_trace(const RtConsts
         // block's backlog at the drain -- what its post-drain tail marches -- is small
         const uint32_t lb_now = (RT_NEAR_UNITS > 0 && vload(q.near_end) != 0u) ? (uint32_t)RT_NEAR_LONG_BATCH : long_batch;
         if (lp >= lb_now || (drained && lp > 0u)) {
-            // (A/B) near the queue's end the long-ray waves issue ahead of the unit waves (RT_LONG_PRIO)
-            if (RT_LONG_PRIO > 0 && lb_now != long_batch) __builtin_amdgcn_s_setprio(RT_LONG_PRIO);
             if constexpr (L == RT_NOMADPLAINS && kSegLanes > 0u) {
-                if (drained && (kSegDrainAll || lp <= kSegQueue)) { // (drain-all: do_shadow refills nothing now)
+                if (drained && lp <= kSegQueue) {
                     do_shadow_seg();
                     WT(const unsigned long long ds = __builtin_amdgcn_s_memrealtime() - t0; wt[4] += ds; wt[7]++;
                        wt[23] += ds; wt[24]++;)
@@ -2136,8 +1954,6 @@ __global__ void __launch_bounds__(TraceThreads<L>::value) k_trace(const RtConsts
                 run = got > 0;
                 if (got < 0) {
                     if (lane == 0) q.drained = 1u;
-                } else if (got == 0 && RT_GATE_SLEEP) { // no ready tile in this step: yield the SIMD to the prepass
-                    __builtin_amdgcn_s_sleep(RT_GATE_SLEEP);
                 } // (0: no ready tile in this step; the next call looks further)
             } else {
                 const uint32_t qi = first_unit ? first_qi : n_static + wave_fetch(&counters[RT_CTR_PRIMARY], lane);
@@ -2443,8 +2259,8 @@ void launch_split_l(const RtLaunch& a, uint32_t ox, uint32_t oy, uint32_t ex, ui
                            a.order, a.hitmask, a.samples, a.fin, a.finpool, a.cpool, a.hitq, a.spill_long, a.hit_cap,
                            a.long_spill_cap, a.aocc, a.queue, a.stats, kLongBatch, kRefillIdle, kCompactLive,
                            a.small_rings ? 64u : kLongRing, a.small_rings ? 8u : kFinSlots, a.fuse_next, a.gated);
-        // fit: every hit pixel is final in k_trace (with its AO ray, by the race of long_finish)
-        if (!(m.fit && (RT_FIT_RACE || a.ao_samples == 0)))
+        // fit without AO: every hit pixel is final in k_trace
+        if (!(m.fit && a.ao_samples == 0))
             hipLaunchKernelGGL(k_finish, dim3(fblocks), blk, 0, a.stream, k0, a.frames, m, a.hitmask, a.samples, a.aocc);
     };
     if (a.stats) primary(std::true_type{});
@@ -2627,9 +2443,8 @@ __global__ void __launch_bounds__(1024) k_rayquery(const RtConsts* __restrict__ 
                                                    float ex, float ey, float ez, uint32_t* __restrict__ counter,
                                                    uint32_t refill_live)
 {
-#ifdef RT_RAYQ_UTIL
-    uint32_t util_wave = 0, util_lane = 0; // this wave's march steps, and its live lanes summed over them
-#endif
+    // (diagnostic) this wave's march steps, and its live lanes summed over them
+    RT_DIAG_RAYQ_UTIL(uint32_t util_wave = 0, util_lane = 0;)
     __shared__ __attribute__((aligned(16))) uint32_t lds[kNoiseLdsWords];
     load_noise_lds(lds, perm2d, grad, k);
     Ctx c = make_ctx(k, lds);
@@ -2661,22 +2476,17 @@ __global__ void __launch_bounds__(1024) k_rayquery(const RtConsts* __restrict__ 
             if (!more) break;
             continue; // every new ray ended before its first step: claim again
         }
-#ifdef RT_RAYQ_UTIL
-        ++util_wave;
-        util_lane += (uint32_t)__popcll(lv);
-#endif
+        RT_DIAG_RAYQ_UTIL(++util_wave; util_lane += (uint32_t)__popcll(lv);)
         if (live) {
             march_step<L, false, true>(c, st);
             live = march_live<L, false, true>(c, st, RT_CAMERA_FAR, 0);
         }
     }
     if (has) store_query_result<STEPS>(st, out, steps, idx);
-#ifdef RT_RAYQ_UTIL
-    if (lane == 0) {
+    RT_DIAG_RAYQ_UTIL(if (lane == 0) {
         atomicAdd(&g_rayq_util[0], (unsigned long long)util_wave);
         atomicAdd(&g_rayq_util[1], (unsigned long long)util_lane);
-    }
-#endif
+    })
 }
 
 } // namespace
@@ -2785,9 +2595,7 @@ __global__ void __launch_bounds__(1024) k_surfquery(const RtConsts* __restrict__
                                                     float4* __restrict__ out, uint32_t* __restrict__ steps, uint32_t n,
                                                     SurfArgs a, uint32_t* __restrict__ counter, uint32_t refill_live)
 {
-#ifdef RT_SURFQ_UTIL
-    uint32_t util_wave = 0, util_lane = 0, util_nwave = 0, util_nlane = 0;
-#endif
+    RT_DIAG_SURFQ_UTIL(uint32_t util_wave = 0, util_lane = 0, util_nwave = 0, util_nlane = 0;)
     __shared__ __attribute__((aligned(16))) uint32_t lds[kNoiseLdsWords];
     load_noise_lds(lds, perm2d, grad, k);
     Ctx c = make_ctx(k, lds);
@@ -2804,12 +2612,10 @@ __global__ void __launch_bounds__(1024) k_surfquery(const RtConsts* __restrict__
         if (more && (uint32_t)__popcll(lv) <= refill_live) {
             const uint32_t cnt = 64u - (uint32_t)__popcll(lv); // >= 1: refill_live <= 63
             const uint32_t first = wave_fetch(counter, lane, cnt);
-#ifdef RT_SURFQ_UTIL
-            if (const uint64_t nm = __ballot(!live && has && st.d > 0.0f)) {
+            RT_DIAG_SURFQ_UTIL(if (const uint64_t nm = __ballot(!live && has && st.d > 0.0f)) {
                 ++util_nwave;
                 util_nlane += (uint32_t)__popcll(nm);
-            }
-#endif
+            })
             if (!live) {
                 if (has) store_surface_result<STEPS>(st, out, steps, idx, normal);
                 idx = first + lane_rank(~lv);
@@ -2828,30 +2634,23 @@ __global__ void __launch_bounds__(1024) k_surfquery(const RtConsts* __restrict__
             if (!more) break;
             continue; // every new ray ended before its first step: claim again
         }
-#ifdef RT_SURFQ_UTIL
-        ++util_wave;
-        util_lane += (uint32_t)__popcll(lv);
-#endif
+        RT_DIAG_SURFQ_UTIL(++util_wave; util_lane += (uint32_t)__popcll(lv);)
         if (live) {
             march_step<L, false, false>(c, st);
             live = march_live<L, false, false>(c, st, endd, a.max_steps);
         }
     }
-#ifdef RT_SURFQ_UTIL
-    if (const uint64_t nm = __ballot(has && st.d > 0.0f)) {
+    RT_DIAG_SURFQ_UTIL(if (const uint64_t nm = __ballot(has && st.d > 0.0f)) {
         ++util_nwave;
         util_nlane += (uint32_t)__popcll(nm);
-    }
-#endif
+    })
     if (has) store_surface_result<STEPS>(st, out, steps, idx, normal);
-#ifdef RT_SURFQ_UTIL
-    if (lane == 0) {
+    RT_DIAG_SURFQ_UTIL(if (lane == 0) {
         atomicAdd(&g_surfq_util[0], (unsigned long long)util_wave);
         atomicAdd(&g_surfq_util[1], (unsigned long long)util_lane);
         atomicAdd(&g_surfq_util[2], (unsigned long long)util_nwave);
         atomicAdd(&g_surfq_util[3], (unsigned long long)util_nlane);
-    }
-#endif
+    })
 }
 
 // the one place a SurfArgs is built: surface and shaded queries alike
@@ -2941,9 +2740,7 @@ __global__ void __launch_bounds__(1024) k_shadequery(const RtConsts* __restrict_
                                                      uint32_t* __restrict__ steps, uint32_t n, SurfArgs a,
                                                      uint32_t* __restrict__ counter, uint32_t refill_live)
 {
-#ifdef RT_SHADEQ_UTIL
-    uint32_t util_wave = 0, util_lane = 0, util_swave = 0, util_slane = 0;
-#endif
+    RT_DIAG_SHADEQ_UTIL(uint32_t util_wave = 0, util_lane = 0, util_swave = 0, util_slane = 0;)
     __shared__ __attribute__((aligned(16))) uint32_t lds[kNoiseLdsWords];
     load_noise_lds(lds, perm2d, grad, k);
     Ctx c = make_ctx(k, lds);
@@ -2964,12 +2761,10 @@ __global__ void __launch_bounds__(1024) k_shadequery(const RtConsts* __restrict_
         uint64_t lv = __ballot(live);
         if ((uint32_t)__popcll(lv) <= refill_live && (more || __ballot(has && !live))) {
             const bool ended = has && !live;
-#ifdef RT_SHADEQ_UTIL
-            if (const uint64_t sm = __ballot(ended && !shadow)) {
+            RT_DIAG_SHADEQ_UTIL(if (const uint64_t sm = __ballot(ended && !shadow)) {
                 ++util_swave;
                 util_slane += (uint32_t)__popcll(sm);
-            }
-#endif
+            })
             if (ended && !shadow) { // tracescreen.hlsl:20-38 after the primary march
                 const RayResult rr = march_result(st);
                 // normalize(dir_i): march_begin's dir * rcp(length(dir)) is rtm::normalize's own product
@@ -3035,23 +2830,18 @@ __global__ void __launch_bounds__(1024) k_shadequery(const RtConsts* __restrict_
             if (!more && !__ballot(has)) break;
             continue; // lanes hold marches that ended before their first step, or there are rays to claim: visit again
         }
-#ifdef RT_SHADEQ_UTIL
-        ++util_wave;
-        util_lane += (uint32_t)__popcll(lv);
-#endif
+        RT_DIAG_SHADEQ_UTIL(++util_wave; util_lane += (uint32_t)__popcll(lv);)
         if (live) {
             march_step_with<L, true, false>(c, st, dens, shadow);
             live = march_live_skip(c, st, endd, shadow ? 0 : a.max_steps, shadow);
         }
     }
-#ifdef RT_SHADEQ_UTIL
-    if (lane == 0) {
+    RT_DIAG_SHADEQ_UTIL(if (lane == 0) {
         atomicAdd(&g_shadeq_util[0], (unsigned long long)util_wave);
         atomicAdd(&g_shadeq_util[1], (unsigned long long)util_lane);
         atomicAdd(&g_shadeq_util[2], (unsigned long long)util_swave);
         atomicAdd(&g_shadeq_util[3], (unsigned long long)util_slane);
-    }
-#endif
+    })
 }
 
 } // namespace

@@ -108,14 +108,7 @@ __device__ __forceinline__ float noise3d_lattice(const NoiseView& nz, uint32_t t
                                                  float x1, float y1, float z, float ux_, float uy_, float uz)
 {
     // Pu = texel + Pu.z per channel (bytes <= 127+127: no carry), % 128
-#if RT_Z_MAD24
-    // (A/B) the replication as one v_mad_u32_u24 (4.2 issue cycles) instead of the v_mad_u64_u32 (4.9) LLVM picks
-    uint32_t w;
-    asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(w) : "v"(Z), "s"(0x01010101u), "v"(t));
-    w &= 0x7f7f7f7fu;
-#else
     uint32_t w = (t + Z * 0x01010101u) & 0x7f7f7f7fu; // AA, AB, BA, BB column indices at z
-#endif
     // entry i of either plane starts at byte i*256: one v_perm_b32 per corner builds
     // base | (index byte << 8) | lane slot ({w, so16} byte pick: 4+k = byte k of w, 0 / 2 = bytes
     // 0 / 2 of so16, 12 = 0); gz is the same address + 32768 (the load's offset field)
@@ -338,55 +331,25 @@ __device__ __forceinline__ float terraces(float s, float y, float steep)
 }
 
 // nomadplains' FBM (terrain.hlsl:16-24): sum over N = 1 .. n_oct of noise3d(q0 * (S, 0.35 S, S)) / S,
-// in octave order (the octave constants come from the LDS image: no scalar loads in the loop).
+// in octave order.
 template <bool FAST>
 __device__ __forceinline__ float np_fbm(const Ctx& c, f3 q0, int n_oct)
 {
     float s = 0.0f;
-#if RT_OCT_SMEM && !defined(RT_EXTRA_OCTAVE)
+#ifndef RT_EXTRA_OCTAVE
     // The octave constants by scalar loads from the launch's constant block: every lane inside the loop
     // is at the same octave N, so N is uniform (an SGPR), and the loop reads no LDS for them (4 LDS-array
-    // cycles of ~40 per octave; rt_variants.h RT_OCT_SMEM)
+    // cycles of ~40 per octave off the CU's LDS: +1.0% Mray/s, profiles/r04/oct_smem_ab.txt).  n_oct >= 2,
+    // so a do-while is exact.
     const KPtr kc = (KPtr)c.k;
     int N = 1;
-#if RT_OCT_SCALAR_EXIT
-    int Ne;
-#endif
     #pragma unroll 1
     do {
         count_noise(c.nz);
         const float sx = kc->np_scale[N], sy = kc->np_scale_y[N], w = kc->np_rcp[N];
         s = fma(noise3d_finish(c.nz, noise3d_cell<FAST>(c.nz, q0.x * sx, q0.y * sy, q0.z * sx)), w, s);
         ++N;
-#if RT_OCT_SCALAR_EXIT
-        // (A/B) the exit compares an opaque SGPR copy of N against each lane's count (one v_cmp), where loop
-        // strength reduction counts every lane down (a v_add and a v_cmp per octave); N itself still
-        // strides the constant loads
-        Ne = N;
-        asm volatile("" : "+s"(Ne));
-    } while (Ne <= n_oct);
-#else
     } while (N <= n_oct);
-#endif
-#elif !defined(RT_EXTRA_OCTAVE)
-    // The octave-table pointer is the trip counter: a per-lane register from the start (the asm
-    // keeps it out of SGPRs, which would cost a v_mov per iteration for the LDS address), one
-    // v_add and one v_cmp against the lane's end per octave.  n_oct >= 2, so a do-while is exact.
-    typedef float v4f __attribute__((ext_vector_type(4)));
-    // volatile: one ds_read_b128 (4 LDS cycles, lane groups of 16 on one broadcast address) rather
-    // than the b96 the compiler narrows an unused .w to (8 cycles: lane groups of 8)
-    typedef __attribute__((address_space(3))) const volatile v4f lds_f4;
-    uint32_t op = (uint32_t)(uintptr_t)(lds_f4*)(c.nz.oct + 1); // LDS byte address of octave 1
-    asm volatile("" : "+v"(op));
-    const uint32_t oe = op + (uint32_t)n_oct * 16u;
-    #pragma unroll 1
-    do {
-        const v4f oc = *(lds_f4*)(uintptr_t)op;
-        count_noise(c.nz);
-        s = fma(noise3d_finish(c.nz, noise3d_cell<FAST>(c.nz, q0.x * oc.x, q0.y * oc.y, q0.z * oc.x)), oc.z, s);
-        op += 16u;
-        asm("" : "+v"(op)); // opaque to loop strength reduction (which would add a second counter)
-    } while (op != oe);
 #else // cost experiment: RT_EXTRA_OCTAVE dead octaves per sample (weight 0: fma(v, 0, s) == s, s is never -0)
     #pragma unroll 1
     for (int N = 1; N <= RT_NP_OCTAVES + RT_EXTRA_OCTAVE; ++N) {
@@ -482,81 +445,6 @@ constexpr float kNoiseBound = RT_NOISE_BOUND;
 // non-zero, and so is its rounding: d < 0.
 constexpr float kSkyCeil = RT_SKY_CEIL;
 
-#if RT_FBM_EXIT
-// (A/B build, rt_variants.h RT_FBM_EXIT) density_nomadplains with an exact early exit.  d = -y + F(s) + G
-// with F(s) = pow(|30 s + 1| 35, expo) and G (terraces + floor lift) independent of the FBM sum s.  After
-// K octaves the rest add at most B (P[n] - P[K]) in magnitude (P: the octave weights' prefix sums, the
-// LDS octave table's w column; B = kNoiseBound >= max |noise3d| for the {-1,0,1} edge gradients).  If
-// every s in that interval gives d in [-5 + m, -m] (m: rounding margin), the march takes the no-hit
-// unit step whatever the exact d is (stepmult = 1 + pow(0, df) = 1), so the sample returns -2.5 in
-// place of d.  `allow` false (the march could exit after this sample) keeps the sample exact; the
-// exact path is density_nomadplains's operation sequence, bit for bit.
-// octaves from LDS table address op up to (not including) oe, as np_fbm's loop
-template <bool FAST>
-__device__ __forceinline__ float fbm_range(const Ctx& c, f3 q0, uint32_t op, uint32_t oe, float s)
-{
-    typedef float v4f __attribute__((ext_vector_type(4)));
-    typedef __attribute__((address_space(3))) const volatile v4f lds_f4;
-    #pragma unroll 1
-    do {
-        const v4f oc = *(lds_f4*)(uintptr_t)op;
-        count_noise(c.nz);
-        s = fma(noise3d_finish(c.nz, noise3d_cell<FAST>(c.nz, q0.x * oc.x, q0.y * oc.y, q0.z * oc.x)), oc.z, s);
-        op += 16u;
-        asm("" : "+v"(op));
-    } while (op != oe);
-    return s;
-}
-__device__ __forceinline__ float density_nomadplains_x(const Ctx& c, f3 p, bool allow)
-{
-    constexpr int K = RT_FBM_EXIT;
-    float d = -p.y;
-    f3 p1 = rtm::scale(p, 0.4f);
-    f3 q0 = rtm::scale(p1, 0.006f);
-    const int n_oct = np_octaves(c, p);
-    const float qm = rtm::max(rtm::max(rtm::abs(q0.x), rtm::abs(q0.y)), rtm::abs(q0.z));
-    const bool fast = !__ballot(!(qm * c.nz.oct[n_oct].x < kFastCellRange));
-    count_noise(c.nz);
-    const float sn = fast ? noise3d_z0<true>(c.nz, p1.x * 0.007138f, p1.z * 0.007138f)
-                          : noise3d_z0<false>(c.nz, p1.x * 0.007138f, p1.z * 0.007138f);
-    const float steep = rtm::sat((sn - 0.2f) * 6.0f) * 7.5f;
-    const float lb = rtm::sat((-p1.y + 10.0f) * 1.6f);
-    const float lift = __ballot(lb != 0.0f) ? rtm::pow_nonneg(lb, 1.5f) : 0.0f;
-    uint32_t op = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) float4*)(c.nz.oct + 1);
-    asm volatile("" : "+v"(op));
-    const int k1 = n_oct < K ? n_oct : K;
-    const uint32_t o1 = op + (uint32_t)k1 * 16u, oe = op + (uint32_t)n_oct * 16u;
-    float s = 0.0f;
-    s = fast ? fbm_range<true>(c, q0, op, o1, s) : fbm_range<false>(c, q0, op, o1, s);
-    op = o1;
-    bool skip = false;
-    const bool cand = allow && n_oct > K;
-    if (__ballot(cand)) {
-        const float G = fma(lift, 19.0f, terraces(0.0f, p1.y, steep));
-        if (cand) {
-            const float m = 0.01f + 1e-5f * rtm::abs(p.y);
-            const float f_hi_ok = p.y - G - m, f_lo_ok = p.y - G - 5.0f + m; // d <= -m, d >= -5 + m
-            const float P = c.nz.oct[n_oct].w - c.nz.oct[K].w;
-            const float R = kNoiseBound * P * 1.0001f + 1e-6f * (rtm::abs(s) + 1.0f);
-            const float u_lo = fma(s - R, 30.0f, 1.0f), u_hi = fma(s + R, 30.0f, 1.0f);
-            const float a_lo = u_lo >= 0.0f ? u_lo : (u_hi <= 0.0f ? -u_hi : 0.0f);
-            const float a_hi = rtm::max(-u_lo, u_hi);
-            const float F_lo = rtm::pow_nonneg(a_lo * 35.0f, c.k->np_expo) * (1.0f - 1e-5f);
-            const float F_hi = rtm::pow_nonneg(a_hi * 35.0f, c.k->np_expo) * (1.0f + 1e-5f);
-            skip = F_lo >= f_lo_ok && F_hi <= f_hi_ok;
-        }
-    }
-    if (!skip && n_oct > k1) {
-        s = fast ? fbm_range<true>(c, q0, op, oe, s) : fbm_range<false>(c, q0, op, oe, s);
-    }
-    if (skip) return -2.5f;
-    s = rtm::pow_nonneg(rtm::abs(fma(s, 30.0f, 1.0f)) * 35.0f, c.k->np_expo);
-    s = terraces(s, p1.y, steep);
-    s = fma(lift, 19.0f, s);
-    return d + s;
-}
-#endif
-
 // density_nomadplains with the FBM spread over a segment of LPR lanes that march ONE
 // ray together (the camerarays prepass: 1024 latency-bound rays for 256 CUs).  The 18 noise values of a sample are numbered
 // v = 0 (the steep noise) and v = N (octave N = 1..17); lane j of the segment evaluates
@@ -646,9 +534,7 @@ __device__ __forceinline__ float density_nomadplains_seg(const Ctx& c, const Seg
         const uint32_t v = (uint32_t)(r * LPR) + j;
         const bool need = v < (uint32_t)NV && (v == 0u || (int)v <= n_oct);
         float n = 0.0f;
-        // RT_SEG_ILP (not LOWREG): every round is evaluated, so the rounds' LDS round trips overlap
-        // (no branch between them); a dead round's value is masked to +0 below
-        if ((RT_SEG_ILP && !LOWREG) || __ballot(need)) {
+        if (__ballot(need)) {
             float sx = g.sx[r], sy = g.sy[r];
             if constexpr (LOWREG) { // the same scales from the LDS octave table, per round (no VGPRs held)
                 typedef __attribute__((address_space(3))) const float lds_f;
@@ -668,7 +554,7 @@ __device__ __forceinline__ float density_nomadplains_seg(const Ctx& c, const Seg
         nv[r] = need ? n : 0.0f;
     }
     float s = 0.0f, on0;
-    constexpr bool kDpp = RT_SEG_DPP && LPR <= 16;
+    constexpr bool kDpp = LPR <= 16;
     if constexpr (kDpp) {
         s = seg_chain_dpp<LPR, 1>(nv, g.rcp, s);
         on0 = nv[0]; // (the first lane's own v = 0)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The amplitude bound behind the RT_FBM_EXIT A/B build (rt_shader.h kNoiseBound).
+"""The amplitude bound behind k_trace's sky exit (rt_shader.h kNoiseBound, used by kSkyCeil and sky_exit).
 
 noise3d (noise.hlsl:153-179, oracle/rt_oracle.c noise3d) blends the eight corner terms
 g_c . (f - c) with the quintic fade weights w_c(f) (non-negative, summing to 1).  The gradient
