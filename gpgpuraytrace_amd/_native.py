@@ -154,6 +154,13 @@ SIGNATURES = {
     "rt_terrain_sample_field_device": (_i, [_vp, _vp, _i, C.POINTER(RtFieldOptions), _vp]),
     "rt_terrain_sample_lattice": (_i, [_vp, C.POINTER(RtLattice), C.POINTER(RtFieldOptions), _vp, _vp]),
     "rt_terrain_sample_lattice_device": (_i, [_vp, C.POINTER(RtLattice), C.POINTER(RtFieldOptions), _vp, _vp]),
+    # mesh extraction: a surface-nets mesh of a lattice (vertices and normals 4 words each, triangles 3 uint32,
+    # counts 2 uint32); the device form takes its scratch block and its size first
+    "rt_terrain_mesh_scratch_bytes": (_sz, [C.POINTER(RtLattice)]),
+    "rt_terrain_extract_mesh": (_i, [_vp, C.POINTER(RtLattice), C.POINTER(RtFieldOptions), _vp, _vp, C.c_uint32, _vp,
+                                     C.c_uint32, _vp]),
+    "rt_terrain_extract_mesh_device": (_i, [_vp, C.POINTER(RtLattice), C.POINTER(RtFieldOptions), _vp, _sz, _vp, _vp,
+                                            C.c_uint32, _vp, C.c_uint32, _vp]),
     "rt_noise_generate": (_i, [C.c_uint32, _i, _vp, _vp]),
     "rt_terrain_set_target_depths": (_i, [_vp, _vp]),
     "rt_recorder_create": (_i, [_vp, _i, _i, _cp, C.POINTER(_vp)]),

@@ -208,6 +208,35 @@ struct RtFieldQuery {
 };
 bool rt_launch_fieldquery(const RtLaunch& a, const RtFieldQuery& q);
 
+// A mesh extraction's passes after the density pass (rt_terrain_extract_mesh; the definition is in
+// include/frosttrace.h, the scratch layout rtq::MeshScratch): the lattice's densities and occupancy words are in
+// `density` and `occupancy` (a lattice RtFieldQuery wrote them on the same stream).  k_meshcount fills `masks`
+// (4 uint64 a mask word) and the words' vertex and quad counts in `offsets` (2 uint32 a word), k_meshscan turns
+// those into the counts preceding each word and writes counts[0..1] (vertices, triangles), k_meshemit stores the
+// first max_vertices vertices (x y z, cell index bits) and the first max_triangles triangles (3 uint32), and with
+// `normals` k_meshnormals stores {getNormal, getDensity} of the first min(counts[0], max_vertices) vertices, with
+// the launch's landscape, tables and constants and `eye` in place of Eye.  All dims >= 2; vertices / triangles
+// may be null with a capacity of 0.  count_blocks and emit_blocks are blocks of rtq::kMeshThreads threads,
+// normal_blocks of 1024.  false: nothing launched.
+struct RtMeshQuery {
+    const float* density;
+    const uint32_t* occupancy;
+    uint64_t* masks;
+    uint32_t* offsets;
+    uint32_t row_words, words; // mask words per cell row and in all
+    float origin[3], spacing[3];
+    uint32_t dims[3];
+    float4* vertices;
+    float4* normals; // may be null: no normal pass
+    uint32_t max_vertices;
+    uint32_t* triangles;
+    uint32_t max_triangles;
+    uint32_t* counts;
+    float eye[3];
+    uint32_t count_blocks, emit_blocks, normal_blocks;
+};
+bool rt_launch_meshquery(const RtLaunch& a, const RtMeshQuery& q);
+
 #define RT_TILE 32
 #define RT_FIN_SLOTS 1536 // k_trace's fin pool slots per block
 #define RT_AO_POOL_SLOTS 256 // k_trace's AO counter slots per block (LDS) and their colours (cpool)

@@ -19,6 +19,7 @@
 #include <type_traits>
 
 #include "rt_kernels.h"
+#include "rt_rayquery.h"
 #include "rt_shader.h"
 #include "rt_variants.h"
 
@@ -2994,6 +2995,266 @@ bool rt_launch_fieldquery(const RtLaunch& a, const RtFieldQuery& q)
             launch_fieldquery<decltype(l_tag)::value, decltype(normal_tag)::value>(a, q);
         });
     });
+    return true;
+}
+
+// ---------------------------------------------------------------------------
+// Mesh extraction (rt_terrain_extract_mesh): a surface-nets mesh of a lattice whose densities and occupancy words
+// k_fieldlattice has written (include/frosttrace.h has the definition, rt_rayquery.h the scratch layout and the
+// mask arithmetic).  Four passes on one stream; the counts stay in device memory and every pass reads them there.
+namespace {
+
+struct MeshGrid {
+    float ox, oy, oz, sx, sy, sz;
+    uint32_t nx, ny, nz;       // points; all >= 2
+    uint32_t row_words, words; // mask words per cell row and in all
+};
+
+// Classification from the occupancy bits alone: one thread per mask word (64 consecutive cx of one cell row)
+// reads the words of the row's four point rows and stores the word's four masks and its vertex and quad counts.
+__global__ void __launch_bounds__(rtq::kMeshThreads) k_meshcount(const uint32_t* __restrict__ occ, uint64_t* __restrict__ masks,
+                                                    uint2* __restrict__ offsets, MeshGrid g)
+{
+    const uint32_t occ_words = (g.nx + 31u) / 32u;
+    for (uint32_t w = blockIdx.x * rtq::kMeshThreads + threadIdx.x; w < g.words; w += gridDim.x * rtq::kMeshThreads) {
+        const uint32_t j = w % g.row_words, row = w / g.row_words, cy = row % (g.ny - 1u), cz = row / (g.ny - 1u);
+        const uint32_t* r00 = occ + ((size_t)cz * g.ny + cy) * occ_words;
+        const uint32_t* r01 = r00 + (size_t)g.ny * occ_words;
+        const rtq::MeshMasks m = rtq::mesh_masks(r00, r00 + occ_words, r01, r01 + occ_words, occ_words, j, g.nx, cy, cz);
+        ulonglong2* out = reinterpret_cast<ulonglong2*>(masks) + 2 * (size_t)w;
+        out[0] = make_ulonglong2(m.active, m.ex);
+        out[1] = make_ulonglong2(m.ey, m.ez);
+        offsets[w] = make_uint2(rtq::mesh_popc(m.active), rtq::mesh_popc(m.ex) + rtq::mesh_popc(m.ey) + rtq::mesh_popc(m.ez));
+    }
+}
+
+__device__ __forceinline__ uint32_t wave_inclusive_sum(uint32_t v, uint32_t lane)
+{
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+        const uint32_t o = __shfl_up(v, d);
+        if (lane >= d) v += o;
+    }
+    return v;
+}
+
+// The exclusive scan of the words' counts, in place, by one block: chunks of 4096 words (4 consecutive words a
+// thread: a wave scan, the 16 wave totals through LDS, the running totals in every thread), then the mesh's totals
+// to counts: vertices, triangles (two a quad).  A lattice of 2^26 points in full rows has 2^20 words: 256 chunks.
+__global__ void __launch_bounds__(1024) k_meshscan(uint2* __restrict__ offsets, uint32_t words,
+                                                   uint32_t* __restrict__ counts)
+{
+    __shared__ uint2 s_wave[16];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t run_v = 0, run_q = 0;
+    uint2 c[4], next[4];
+    auto load = [&](uint32_t base, uint2(&into)[4]) {
+#pragma unroll
+        for (uint32_t i = 0; i < 4u; ++i) {
+            const uint32_t w = base + threadIdx.x * 4u + i;
+            into[i] = w < words ? offsets[w] : make_uint2(0u, 0u);
+        }
+    };
+    load(0u, c);
+    for (uint32_t base = 0; base < words; base += 4096u) {
+        const uint32_t w0 = base + threadIdx.x * 4u;
+        load(base + 4096u, next); // the next chunk's counts arrive while this one is scanned
+        uint32_t tv = 0, tq = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < 4u; ++i) {
+            tv += c[i].x;
+            tq += c[i].y;
+        }
+        const uint32_t iv = wave_inclusive_sum(tv, lane), iq = wave_inclusive_sum(tq, lane);
+        if (lane == 63u) s_wave[wave] = make_uint2(iv, iq);
+        __syncthreads();
+        uint32_t ev = run_v + iv - tv, eq = run_q + iq - tq; // what precedes this thread's first word
+#pragma unroll
+        for (uint32_t k = 0; k < 16u; ++k) {
+            const uint2 t = s_wave[k];
+            if (k < wave) {
+                ev += t.x;
+                eq += t.y;
+            }
+            run_v += t.x;
+            run_q += t.y;
+        }
+#pragma unroll
+        for (uint32_t i = 0; i < 4u; ++i) {
+            if (w0 + i < words) offsets[w0 + i] = make_uint2(ev, eq);
+            ev += c[i].x;
+            eq += c[i].y;
+        }
+#pragma unroll
+        for (uint32_t i = 0; i < 4u; ++i) c[i] = next[i];
+        __syncthreads(); // s_wave is rewritten by the next chunk
+    }
+    if (threadIdx.x == 0) {
+        counts[0] = run_v;
+        counts[1] = 2u * run_q;
+    }
+}
+
+// the index of the vertex of active cell (cx, cy, cz): the vertices before its word and those of the word's lower bits
+__device__ __forceinline__ uint32_t mesh_vertex_index(const uint64_t* __restrict__ masks, const uint2* __restrict__ offsets,
+                                                      const MeshGrid& g, uint32_t cx, uint32_t cy, uint32_t cz)
+{
+    const size_t w = ((size_t)cz * (g.ny - 1u) + cy) * g.row_words + (cx >> 6);
+    return offsets[w].x + rtq::mesh_popc(masks[4 * w] & ((1ull << (cx & 63u)) - 1ull));
+}
+
+// one crossing of a cell: edge E (0..11, the header's order) between corners A and B of the 8 densities d
+template <int E>
+__device__ __forceinline__ void mesh_crossing(const float (&d)[8], float& sx, float& sy, float& sz, uint32_t& n)
+{
+    constexpr int AXIS = E >> 2, P = E & 1, Q = (E >> 1) & 1;
+    // the corner offsets on the other two axes, the lower axis first
+    constexpr int KX = AXIS == 0 ? 0 : P, KY = AXIS == 0 ? P : (AXIS == 1 ? 0 : Q), KZ = AXIS == 2 ? 0 : Q;
+    constexpr int A = KX + 2 * KY + 4 * KZ, B = A + (1 << AXIS);
+    const float da = d[A], db = d[B];
+    if ((da > 0.0f) != (db > 0.0f)) {
+        const float t = __fdiv_rn(da, __fsub_rn(da, db));
+        sx = __fadd_rn(sx, AXIS == 0 ? t : (float)KX);
+        sy = __fadd_rn(sy, AXIS == 1 ? t : (float)KY);
+        sz = __fadd_rn(sz, AXIS == 2 ? t : (float)KZ);
+        ++n;
+    }
+}
+
+// the two triangles of quad q over the vertices A B C D, wound by the lower endpoint's side
+__device__ __forceinline__ void mesh_store_quad(uint32_t* __restrict__ tri, uint32_t max_triangles, uint32_t q,
+                                                bool inside, uint32_t A, uint32_t B, uint32_t C, uint32_t D)
+{
+    const uint32_t second = inside ? B : D, fourth = inside ? D : B;
+    uint32_t* t = tri + 6 * (size_t)q;
+    if (2u * q < max_triangles) {
+        t[0] = A;
+        t[1] = second;
+        t[2] = C;
+    }
+    if (2u * q + 1u < max_triangles) {
+        t[3] = A;
+        t[4] = C;
+        t[5] = fourth;
+    }
+}
+
+// Vertices and indices: a wave takes a mask word, a lane a cell.  An active cell reads its 8 densities, places its
+// vertex and stores it at the word's offset plus the active cells below it in the word; each edge bit stores its
+// quad's 6 indices at the word's quad offset plus the edge bits below it in (cell, axis) order.  Every store is
+// guarded by its capacity.
+__global__ void __launch_bounds__(rtq::kMeshThreads) k_meshemit(const float* __restrict__ dens, const uint64_t* __restrict__ masks,
+                                                   const uint2* __restrict__ offsets, MeshGrid g,
+                                                   float4* __restrict__ vertices, uint32_t max_vertices,
+                                                   uint32_t* __restrict__ tri, uint32_t max_triangles)
+{
+    const uint32_t lane = threadIdx.x & 63u, waves = blockDim.x >> 6;
+    const uint64_t below = (1ull << lane) - 1ull;
+    for (uint32_t w = blockIdx.x * waves + (threadIdx.x >> 6); w < g.words; w += gridDim.x * waves) {
+        const uint64_t act = masks[4 * (size_t)w];
+        if (!((act >> lane) & 1ull)) continue; // (every cell with an edge bit is active)
+        const uint64_t ex = masks[4 * (size_t)w + 1], ey = masks[4 * (size_t)w + 2], ez = masks[4 * (size_t)w + 3];
+        const uint2 off = offsets[w];
+        const uint32_t j = w % g.row_words, row = w / g.row_words, cy = row % (g.ny - 1u), cz = row / (g.ny - 1u);
+        const uint32_t cx = j * 64u + lane;
+        const size_t p0 = ((size_t)cz * g.ny + cy) * g.nx + cx, dy = g.nx, dz = (size_t)g.nx * g.ny;
+        const float d[8] = {dens[p0],      dens[p0 + 1],      dens[p0 + dy],      dens[p0 + dy + 1],
+                            dens[p0 + dz], dens[p0 + dz + 1], dens[p0 + dz + dy], dens[p0 + dz + dy + 1]};
+        float lx = 0.0f, ly = 0.0f, lz = 0.0f;
+        uint32_t n = 0;
+        mesh_crossing<0>(d, lx, ly, lz, n);
+        mesh_crossing<1>(d, lx, ly, lz, n);
+        mesh_crossing<2>(d, lx, ly, lz, n);
+        mesh_crossing<3>(d, lx, ly, lz, n);
+        mesh_crossing<4>(d, lx, ly, lz, n);
+        mesh_crossing<5>(d, lx, ly, lz, n);
+        mesh_crossing<6>(d, lx, ly, lz, n);
+        mesh_crossing<7>(d, lx, ly, lz, n);
+        mesh_crossing<8>(d, lx, ly, lz, n);
+        mesh_crossing<9>(d, lx, ly, lz, n);
+        mesh_crossing<10>(d, lx, ly, lz, n);
+        mesh_crossing<11>(d, lx, ly, lz, n);
+        const float cnt = (float)n;
+        lx = __fdiv_rn(lx, cnt);
+        ly = __fdiv_rn(ly, cnt);
+        lz = __fdiv_rn(lz, cnt);
+        const uint32_t vi = off.x + rtq::mesh_popc(act & below);
+        if (vi < max_vertices) {
+            const uint32_t cell = (cz * (g.ny - 1u) + cy) * (g.nx - 1u) + cx;
+            gstore(vertices + vi, make_float4(fmaf(__fadd_rn((float)cx, lx), g.sx, g.ox),
+                                              fmaf(__fadd_rn((float)cy, ly), g.sy, g.oy),
+                                              fmaf(__fadd_rn((float)cz, lz), g.sz, g.oz), __uint_as_float(cell)));
+        }
+        const uint32_t bx = (uint32_t)(ex >> lane) & 1u, by = (uint32_t)(ey >> lane) & 1u, bz = (uint32_t)(ez >> lane) & 1u;
+        if (!(bx | by | bz)) continue;
+        const uint32_t q = off.y + rtq::mesh_popc(ex & below) + rtq::mesh_popc(ey & below) + rtq::mesh_popc(ez & below);
+        const bool inside = d[0] > 0.0f;
+        // the cells around the edge from corner 0 along the axis: A = c - u - v, B = c - v, C = c, D = c - u with
+        // (u, v) the next two axes in cyclic order
+        if (bx) // u = y, v = z
+            mesh_store_quad(tri, max_triangles, q, inside, mesh_vertex_index(masks, offsets, g, cx, cy - 1u, cz - 1u),
+                            mesh_vertex_index(masks, offsets, g, cx, cy, cz - 1u), vi,
+                            mesh_vertex_index(masks, offsets, g, cx, cy - 1u, cz));
+        if (by) // u = z, v = x
+            mesh_store_quad(tri, max_triangles, q + bx, inside, mesh_vertex_index(masks, offsets, g, cx - 1u, cy, cz - 1u),
+                            mesh_vertex_index(masks, offsets, g, cx - 1u, cy, cz), vi,
+                            mesh_vertex_index(masks, offsets, g, cx, cy, cz - 1u));
+        if (bz) // u = x, v = y
+            mesh_store_quad(tri, max_triangles, q + bx + by, inside,
+                            mesh_vertex_index(masks, offsets, g, cx - 1u, cy - 1u, cz),
+                            mesh_vertex_index(masks, offsets, g, cx, cy - 1u, cz), vi,
+                            mesh_vertex_index(masks, offsets, g, cx - 1u, cy, cz));
+    }
+}
+
+// The normal pass: k_fieldpoints over the compacted vertices (x y z, the cell word ignored) -> {getNormal,
+// getDensity}, its bound min(counts[0], max_vertices) read from device memory.
+template <int L>
+__global__ void __launch_bounds__(1024) k_meshnormals(const RtConsts* __restrict__ k, const uint32_t* __restrict__ perm2d,
+                                                      const float4* __restrict__ grad,
+                                                      const float4* __restrict__ vertices, float4* __restrict__ out,
+                                                      const uint32_t* __restrict__ counts, uint32_t max_vertices,
+                                                      FieldEye e)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t lds[kNoiseLdsWords];
+    load_noise_lds(lds, perm2d, grad, k);
+    Ctx c = make_ctx(k, lds);
+    c.eye = rtm::mk(e.x, e.y, e.z);
+    const uint32_t have = counts[0], n = have < max_vertices ? have : max_vertices;
+    const uint32_t tiles = (n + 1023u) / 1024u;
+    for (uint32_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const uint32_t i = t * 1024u + threadIdx.x;
+        if (i < n) {
+            const float4 q = vertices[i];
+            const f3 p = rtm::mk(q.x, q.y, q.z);
+            store_field_result<L, true>(c, p, get_density<L>(c, p), out, i);
+        }
+    }
+}
+
+} // namespace
+
+bool rt_launch_meshquery(const RtLaunch& a, const RtMeshQuery& q)
+{
+    if (q.words == 0 || q.dims[0] < 2u || q.dims[1] < 2u || q.dims[2] < 2u) return false;
+    if (!q.density || !q.occupancy || !q.masks || !q.offsets || !q.counts) return false;
+    if ((q.max_vertices && !q.vertices) || (q.max_triangles && !q.triangles)) return false;
+    if (q.count_blocks == 0 || q.emit_blocks == 0 || (q.normals && q.max_vertices && q.normal_blocks == 0)) return false;
+    const MeshGrid g{q.origin[0], q.origin[1], q.origin[2], q.spacing[0], q.spacing[1], q.spacing[2],
+                     q.dims[0],   q.dims[1],   q.dims[2],   q.row_words,  q.words};
+    uint2* offsets = reinterpret_cast<uint2*>(q.offsets);
+    hipLaunchKernelGGL(k_meshcount, dim3(q.count_blocks), dim3(rtq::kMeshThreads), 0, a.stream, q.occupancy, q.masks, offsets, g);
+    hipLaunchKernelGGL(k_meshscan, dim3(1), dim3(1024), 0, a.stream, offsets, q.words, q.counts);
+    if (q.max_vertices || q.max_triangles) // (a counting call stores nothing)
+        hipLaunchKernelGGL(k_meshemit, dim3(q.emit_blocks), dim3(rtq::kMeshThreads), 0, a.stream, q.density, q.masks, offsets, g,
+                           q.vertices, q.max_vertices, q.triangles, q.max_triangles);
+    if (q.normals && q.max_vertices) {
+        const FieldEye e{q.eye[0], q.eye[1], q.eye[2]};
+        with_landscape(a, [&](auto l_tag) {
+            hipLaunchKernelGGL((k_meshnormals<decltype(l_tag)::value>), dim3(q.normal_blocks), dim3(1024), 0, a.stream,
+                               a.consts, a.perm2d, a.grad, q.vertices, q.normals, q.counts, q.max_vertices, e);
+        });
+    }
     return true;
 }
 

@@ -1,9 +1,10 @@
 // rt_rayquery.h -- host-only decisions of rt_terrain_trace_rays, rt_terrain_trace_surface,
 // rt_terrain_shade_rays and the field queries rt_terrain_sample_field / rt_terrain_sample_lattice
 // (include/frosttrace.h): the option blocks' validation, the choice of the kernel shape, its lanes per ray,
-// its strips and its grid, and the layout of the host forms' device block.  No HIP in here:
-// tests/tools/rayquery_check.cpp, surfquery_check.cpp, shadequery_check.cpp, fieldquery_check.cpp and
-// querylayout_check.cpp drive it stand-alone under ASan + UBSan.
+// its strips and its grid, the layout of the host forms' device block, and the scratch layout, grids and mask
+// arithmetic of rt_terrain_extract_mesh.  No HIP in here (the mask arithmetic is marked __host__ __device__ under
+// hipcc only, for k_meshcount): tests/tools/rayquery_check.cpp, surfquery_check.cpp, shadequery_check.cpp,
+// fieldquery_check.cpp, meshquery_check.cpp and querylayout_check.cpp drive it stand-alone under ASan + UBSan.
 #pragma once
 
 #include <cstddef>
@@ -326,9 +327,9 @@ inline size_t occupancy_bytes(const uint32_t dims[3])
     return (size_t)((dims[0] + 31u) / 32u) * dims[1] * dims[2] * 4;
 }
 
-constexpr int kBlockParts = 4;
+constexpr int kBlockParts = 5;
 struct BlockLayout {
-    size_t offset[kBlockParts] = {0, 0, 0, 0};
+    size_t offset[kBlockParts] = {};
     size_t total = 0;
 };
 
@@ -380,6 +381,108 @@ inline void pack(const float* origins, const float* dirs, int n, float* packed)
         r[6] = dirs[3 * (size_t)i + 2];
         r[7] = 0.0f;
     }
+}
+
+// ---- mesh extraction (rt_terrain_extract_mesh): a surface-nets mesh of a lattice's density ----
+//
+// A cell row is the cells (cx, cy, cz) of one (cy, cz); it is cut into mask words of 64 consecutive cx, so bit b of
+// word j of a row is cell cx = 64 j + b.  A word carries four 64-bit masks (MeshMasks) and, after the scan, the
+// number of vertices and of quads that precede it in cell order.
+
+// the masks of one word: active cells, and the cells whose corner-0 edge along x / y / z crosses the surface and is
+// interior (the other two cell coordinates >= 1): each such bit is one quad
+struct MeshMasks {
+    uint64_t active, ex, ey, ez;
+};
+constexpr size_t kMeshMaskBytes = 32, kMeshOffsetBytes = 8, kMeshVertexBytes = 16, kMeshTriangleBytes = 12;
+
+#if defined(__HIPCC__)
+#define RTQ_HD __host__ __device__
+#else
+#define RTQ_HD
+#endif
+
+// points 64 j .. 64 j + 63 of an occupancy row of occ_words words (the padding bits are 0) in *lo, and the same
+// shifted by one point, 64 j + 1 .. 64 j + 64, in *hi; points beyond the row read as 0
+RTQ_HD inline void mesh_row_bits(const uint32_t* row, uint32_t occ_words, uint32_t j, uint64_t* lo, uint64_t* hi)
+{
+    const uint32_t w = 2u * j;
+    const uint64_t w0 = w < occ_words ? row[w] : 0u, w1 = w + 1u < occ_words ? row[w + 1u] : 0u,
+                   w2 = w + 2u < occ_words ? row[w + 2u] : 0u;
+    *lo = w0 | (w1 << 32);
+    *hi = (*lo >> 1) | ((w2 & 1u) << 63);
+}
+
+// The masks of word j of cell row (cy, cz) of a lattice of nx points a row (64 j < nx - 1), from the occupancy
+// rows of its four point rows: r00 = (cy, cz), r10 = (cy + 1, cz), r01 = (cy, cz + 1), r11 = (cy + 1, cz + 1).
+RTQ_HD inline MeshMasks mesh_masks(const uint32_t* r00, const uint32_t* r10, const uint32_t* r01, const uint32_t* r11,
+                                   uint32_t occ_words, uint32_t j, uint32_t nx, uint32_t cy, uint32_t cz)
+{
+    uint64_t l00, h00, l10, h10, l01, h01, l11, h11;
+    mesh_row_bits(r00, occ_words, j, &l00, &h00);
+    mesh_row_bits(r10, occ_words, j, &l10, &h10);
+    mesh_row_bits(r01, occ_words, j, &l01, &h01);
+    mesh_row_bits(r11, occ_words, j, &l11, &h11);
+    const uint32_t cells = nx - 1u - 64u * j; // of this word and the row's later ones
+    const uint64_t valid = cells >= 64u ? ~0ull : (1ull << cells) - 1ull;
+    const uint64_t any = l00 | h00 | l10 | h10 | l01 | h01 | l11 | h11;
+    const uint64_t all = l00 & h00 & l10 & h10 & l01 & h01 & l11 & h11;
+    const uint64_t x_in = j ? valid : valid & ~1ull; // cx >= 1
+    MeshMasks m;
+    m.active = any & ~all & valid;
+    m.ex = cy >= 1u && cz >= 1u ? (l00 ^ h00) & valid : 0ull;
+    m.ey = cz >= 1u ? (l00 ^ l10) & x_in : 0ull;
+    m.ez = cy >= 1u ? (l00 ^ l01) & x_in : 0ull;
+    return m;
+}
+
+RTQ_HD inline uint32_t mesh_popc(uint64_t m) { return (uint32_t)__builtin_popcountll(m); }
+
+// The scratch block of a mesh extraction, laid out by block_layout: the lattice's densities (one float a point),
+// its occupancy words, the mask words (MeshMasks each) and a uint32 pair per mask word -- the word's vertex and
+// quad counts, which the scan replaces by the counts that precede the word.
+struct MeshScratch {
+    uint32_t points = 0;    // nx ny nz
+    uint32_t cells = 0;     // (nx - 1)(ny - 1)(nz - 1), 0 when a dim is below 2
+    uint32_t row_words = 0; // mask words per cell row: ceil((nx - 1) / 64)
+    uint32_t words = 0;     // row_words (ny - 1)(nz - 1): about points / 64 (2^20 at most) unless the rows are short
+    BlockLayout lay;        // parts: densities, occupancy, masks, offsets; total 0 without cells
+};
+enum { MESH_DENSITY = 0, MESH_OCCUPANCY = 1, MESH_MASKS = 2, MESH_OFFSETS = 3 };
+
+// dims of a lattice that check_lattice passed
+inline MeshScratch mesh_scratch(const uint32_t dims[3])
+{
+    MeshScratch s;
+    s.points = dims[0] * dims[1] * dims[2];
+    if (dims[0] < 2u || dims[1] < 2u || dims[2] < 2u) return s;
+    s.cells = (dims[0] - 1u) * (dims[1] - 1u) * (dims[2] - 1u);
+    s.row_words = (dims[0] - 1u + 63u) / 64u;
+    s.words = s.row_words * (dims[1] - 1u) * (dims[2] - 1u);
+    const size_t bytes[4] = {(size_t)s.points * 4, occupancy_bytes(dims), (size_t)s.words * kMeshMaskBytes,
+                             (size_t)s.words * kMeshOffsetBytes};
+    s.lay = block_layout(bytes, 4);
+    return s;
+}
+
+// The grids of the passes after the density pass; a block strides over the work.  The count pass takes a mask word
+// a thread and the emit pass a word a wave, both in blocks of kMeshThreads threads: light kernels without LDS, eight
+// blocks a CU resident, so their grid is capped at 8 blocks a CU (or at max_blocks).  The normal pass is a field
+// kernel (1024 threads, the noise tables in LDS, a block a CU) over at most `vertices` vertices: the capacity, and
+// no more than the cells.
+constexpr uint32_t kMeshThreads = 256u, kMeshWaves = kMeshThreads / 64u;
+struct MeshPlan {
+    uint32_t count_blocks = 0, emit_blocks = 0, normal_blocks = 0;
+};
+inline MeshPlan plan_mesh(const MeshScratch& s, uint32_t max_vertices, uint32_t max_blocks, int cus)
+{
+    MeshPlan p;
+    const int light = 8 * (cus > 0 ? cus : 1);
+    p.count_blocks = field_grid((s.words + kMeshThreads - 1u) / kMeshThreads, max_blocks, light);
+    p.emit_blocks = field_grid((s.words + kMeshWaves - 1u) / kMeshWaves, max_blocks, light);
+    const uint32_t v = max_vertices < s.cells ? max_vertices : s.cells;
+    p.normal_blocks = field_grid((v + 1023u) / 1024u, max_blocks, cus);
+    return p;
 }
 
 } // namespace rtq

@@ -3295,6 +3295,159 @@ extern "C" int rt_terrain_sample_lattice(rt_compute c, const rt_lattice* lat, co
 }
 
 // ---------------------------------------------------------------------------
+// rt_terrain_extract_mesh: a surface-nets mesh of a lattice's density (include/frosttrace.h): the lattice query's
+// density and occupancy pass into the scratch block, then the mesh passes (rt_launch_meshquery), all on the device
+// stream; the counts stay in device memory.
+namespace {
+
+// enqueue one extraction (no host synchronisation, no allocation); the scratch block holds s.lay.total bytes
+int extract_mesh_enqueue(rt_compute c, const rtq::Lattice& l, const rtq::MeshScratch& s, const rtq::FieldOptions& o,
+                         char* scratch, void* vertices, void* normals, uint32_t max_vertices, void* triangles,
+                         uint32_t max_triangles, void* counts)
+{
+    rt_device dev = c->dev;
+    if (s.cells == 0) { // no cells: the counts are all there is to write
+        HIP_TRY(hipMemsetAsync(counts, 0, 2 * sizeof(uint32_t), dev->stream));
+        return RT_OK;
+    }
+    rtq::FieldOptions density_opt = o;
+    density_opt.flags &= ~rtq::kFieldNormal;
+    if (int rc = sample_field_enqueue(c, nullptr, &l, s.points, density_opt, scratch + s.lay.offset[rtq::MESH_DENSITY],
+                                      scratch + s.lay.offset[rtq::MESH_OCCUPANCY]))
+        return rc;
+    RtLaunch a;
+    RtMeshQuery q{};
+    if (int rc = query_prepare(c, o, false, &a, q.eye)) return rc;
+    q.density = (const float*)(scratch + s.lay.offset[rtq::MESH_DENSITY]);
+    q.occupancy = (const uint32_t*)(scratch + s.lay.offset[rtq::MESH_OCCUPANCY]);
+    q.masks = (uint64_t*)(scratch + s.lay.offset[rtq::MESH_MASKS]);
+    q.offsets = (uint32_t*)(scratch + s.lay.offset[rtq::MESH_OFFSETS]);
+    q.row_words = s.row_words;
+    q.words = s.words;
+    memcpy(q.origin, l.origin, sizeof(q.origin));
+    memcpy(q.spacing, l.spacing, sizeof(q.spacing));
+    memcpy(q.dims, l.dims, sizeof(q.dims));
+    q.vertices = (float4*)vertices;
+    q.normals = (float4*)normals;
+    q.max_vertices = max_vertices;
+    q.triangles = (uint32_t*)triangles;
+    q.max_triangles = max_triangles;
+    q.counts = (uint32_t*)counts;
+    const rtq::MeshPlan p = rtq::plan_mesh(s, max_vertices, o.max_blocks, cus_of(dev));
+    q.count_blocks = p.count_blocks;
+    q.emit_blocks = p.emit_blocks;
+    q.normal_blocks = p.normal_blocks;
+    return query_launched(rt_launch_meshquery(a, q), "rt_terrain_extract_mesh: no kernel for this query");
+}
+
+// The blocking form: one device block (the scratch, the three arrays at their capacities, the counts), the
+// extraction, the counts' download and then the written prefixes' -- min(count, capacity) entries, so the host
+// arrays keep what lies beyond them.
+int extract_mesh_host(rt_compute c, const rtq::Lattice& l, const rtq::MeshScratch& s, const rtq::FieldOptions& o,
+                      float* vertices, float* normals, uint32_t max_vertices, uint32_t* triangles,
+                      uint32_t max_triangles, uint32_t* counts)
+{
+    rt_device dev = c->dev;
+    if (s.cells == 0) {
+        counts[0] = counts[1] = 0;
+        return RT_OK;
+    }
+    const size_t bytes[] = {s.lay.total, max_vertices * rtq::kMeshVertexBytes,
+                            normals ? max_vertices * rtq::kMeshVertexBytes : 0, max_triangles * rtq::kMeshTriangleBytes,
+                            2 * sizeof(uint32_t)};
+    const rtq::BlockLayout lay = rtq::block_layout(bytes, 5);
+    char* d = nullptr;
+    HIP_TRY(hipMalloc(&d, lay.total));
+    auto at = [&](int i) { return bytes[i] ? d + lay.offset[i] : nullptr; };
+    auto run = [&]() -> int {
+        if (int rc = extract_mesh_enqueue(c, l, s, o, at(0), at(1), at(2), max_vertices, at(3), max_triangles, at(4)))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(counts, at(4), bytes[4], hipMemcpyDeviceToHost, dev->stream));
+        HIP_TRY(hipStreamSynchronize(dev->stream));
+        const size_t nv = counts[0] < max_vertices ? counts[0] : max_vertices;
+        const size_t nt = counts[1] < max_triangles ? counts[1] : max_triangles;
+        if (nv) HIP_TRY(hipMemcpyAsync(vertices, at(1), nv * rtq::kMeshVertexBytes, hipMemcpyDeviceToHost, dev->stream));
+        if (nv && normals)
+            HIP_TRY(hipMemcpyAsync(normals, at(2), nv * rtq::kMeshVertexBytes, hipMemcpyDeviceToHost, dev->stream));
+        if (nt) HIP_TRY(hipMemcpyAsync(triangles, at(3), nt * rtq::kMeshTriangleBytes, hipMemcpyDeviceToHost, dev->stream));
+        HIP_TRY(hipStreamSynchronize(dev->stream));
+        return RT_OK;
+    };
+    const int rc = run();
+    if (rc) (void)hipStreamSynchronize(dev->stream); // whatever was queued is over before the block is freed
+    (void)hipFree(d);
+    return rc;
+}
+
+// both entry points; scratch null: the host form
+int extract_mesh_entry(const char* who, rt_compute c, const rt_lattice* lat, const rt_field_options* opt, void* scratch,
+                       size_t scratch_bytes, void* vertices, void* normals, uint32_t max_vertices, void* triangles,
+                       uint32_t max_triangles, void* counts, bool host)
+{
+    const QueryFamily<rtq::FieldOptions> f{who, nullptr, rtq::parse_field_options};
+    rtq::Lattice l;
+    rtq::MeshScratch s;
+    return query_entry(
+        c, f, 0, opt,
+        [&](const rtq::FieldOptions&, uint32_t* n) -> int {
+            const char* why = "";
+            uint32_t points = 0;
+            if (int rc = rtq::check_lattice(lat, &l, &points, &why)) return fail(rc, "%s: %s", who, why);
+            s = rtq::mesh_scratch(l.dims);
+            if (!counts) return fail(RT_ERR_INVALID, "%s: null counts", who);
+            if ((max_vertices && !vertices) || (max_triangles && !triangles))
+                return fail(RT_ERR_INVALID, "%s: a capacity above 0 with a null array", who);
+            if (!host && s.lay.total) {
+                if (!scratch || scratch_bytes < s.lay.total)
+                    return fail(RT_ERR_INVALID, "%s: the scratch block is null or below rt_terrain_mesh_scratch_bytes", who);
+                if (((uintptr_t)scratch | (uintptr_t)vertices | (uintptr_t)normals) % 16)
+                    return fail(RT_ERR_INVALID, "%s: scratch, vertices and normals must be 16-byte aligned", who);
+            }
+            *n = 1; // one call: a lattice without cells still gets its counts written
+            return RT_OK;
+        },
+        nullptr,
+        [&](const rtq::FieldOptions& o, uint32_t) {
+            // a mesh has a vertex per cell and three quads per cell at most: a larger capacity holds no more
+            if (max_vertices > s.cells) max_vertices = s.cells;
+            if (max_triangles > 6u * s.cells) max_triangles = 6u * s.cells;
+            if (host)
+                return extract_mesh_host(c, l, s, o, (float*)vertices, (float*)normals, max_vertices, (uint32_t*)triangles,
+                                         max_triangles, (uint32_t*)counts);
+            return extract_mesh_enqueue(c, l, s, o, (char*)scratch, vertices, normals, max_vertices, triangles,
+                                        max_triangles, counts);
+        });
+}
+
+} // namespace
+
+extern "C" size_t rt_terrain_mesh_scratch_bytes(const rt_lattice* lat)
+{
+    rtq::Lattice l;
+    uint32_t n = 0;
+    const char* why = "";
+    if (rtq::check_lattice(lat, &l, &n, &why)) return 0;
+    return rtq::mesh_scratch(l.dims).lay.total;
+}
+
+extern "C" int rt_terrain_extract_mesh(rt_compute c, const rt_lattice* lat, const rt_field_options* opt, float* vertices,
+                                       float* normals, uint32_t max_vertices, uint32_t* triangles, uint32_t max_triangles,
+                                       uint32_t counts[2])
+{
+    return extract_mesh_entry("rt_terrain_extract_mesh", c, lat, opt, nullptr, 0, vertices, normals, max_vertices,
+                              triangles, max_triangles, counts, true);
+}
+
+extern "C" int rt_terrain_extract_mesh_device(rt_compute c, const rt_lattice* lat, const rt_field_options* opt,
+                                              void* scratch_device, size_t scratch_bytes, void* vertices_device,
+                                              void* normals_device, uint32_t max_vertices, void* triangles_device,
+                                              uint32_t max_triangles, void* counts_device)
+{
+    return extract_mesh_entry("rt_terrain_extract_mesh_device", c, lat, opt, scratch_device, scratch_bytes, vertices_device,
+                              normals_device, max_vertices, triangles_device, max_triangles, counts_device, false);
+}
+
+// ---------------------------------------------------------------------------
 // rt_readback_*: the asynchronous readback ring (struct rt_readback_s above; include/frosttrace.h)
 int rt_readback_create(rt_device d, int format, int depth, rt_readback* out)
 {

@@ -810,6 +810,56 @@ class Terrain:
                                                     results_ptr or None, occupancy_ptr or None)
         return rc == _native.RT_OK
 
+    def extract_mesh(self, origin, spacing, dims, eye=None, normals=True, max_blocks=0):
+        """rt_terrain_extract_mesh: the terrain's surface inside the lattice (sample_lattice's origin, spacing and
+        dims) as a surface-nets triangle mesh, extracted on the device.  Returns (vertices (nv, 3) float32,
+        normals (nv, 4) float32 rows getNormal xyz, density -- or None without normals --, triangles (nt, 3) uint32
+        wound so that their normals point out of the terrain, cells (nv,) uint32: each vertex's cell index
+        (cz (ny - 1) + cy) (nx - 1) + cx); None if a call fails.  Two calls: one that counts and one of the exact
+        size, so the lattice's density is computed twice; keep the arrays on the device and size them yourself
+        (extract_mesh_device) where that matters.  Blocking; uses the camerarays compute."""
+        lat = lattice(origin, spacing, dims)
+        opt = field_options(eye, False, max_blocks)
+        self.update_shaders()
+        counts = np.zeros(2, np.uint32)
+        cs = self.camera_compute._h
+        if lib().rt_terrain_extract_mesh(cs, C.byref(lat), C.byref(opt), None, None, 0, None, 0,
+                                         counts.ctypes.data) != _native.RT_OK:
+            return None
+        nv, nt = int(counts[0]), int(counts[1])
+        verts = np.zeros((nv, 4), np.float32)
+        nrm = np.zeros((nv, 4), np.float32) if normals else None
+        tris = np.zeros((nt, 3), np.uint32)
+        rc = lib().rt_terrain_extract_mesh(cs, C.byref(lat), C.byref(opt), verts.ctypes.data if nv else None,
+                                           nrm.ctypes.data if normals and nv else None, nv,
+                                           tris.ctypes.data if nt else None, nt, counts.ctypes.data)
+        if rc != _native.RT_OK or (int(counts[0]), int(counts[1])) != (nv, nt):
+            return None
+        return np.ascontiguousarray(verts[:, :3]), nrm, tris, np.ascontiguousarray(verts[:, 3]).view(np.uint32)
+
+    def extract_mesh_device(self, origin, spacing, dims, scratch_ptr, scratch_bytes, vertices_ptr, normals_ptr,
+                            max_vertices, triangles_ptr, max_triangles, counts_ptr, eye=None, max_blocks=0):
+        """rt_terrain_extract_mesh_device: the same into device arrays -- scratch_ptr at least
+        mesh_scratch_bytes(origin, spacing, dims) bytes, vertices_ptr max_vertices x 4 words (x y z, cell index
+        bits), normals_ptr the same shape or 0 (no normal pass), triangles_ptr max_triangles x 3 uint32, counts_ptr
+        2 uint32 (the full vertex and triangle counts); scratch, vertices and normals 16-byte aligned -- enqueued
+        on the device's stream with no host synchronisation and no allocation.  True on success."""
+        lat = lattice(origin, spacing, dims)
+        opt = field_options(eye, False, max_blocks)
+        self.update_shaders()
+        rc = lib().rt_terrain_extract_mesh_device(self.camera_compute._h, C.byref(lat), C.byref(opt),
+                                                  scratch_ptr or None, int(scratch_bytes), vertices_ptr or None,
+                                                  normals_ptr or None, int(max_vertices), triangles_ptr or None,
+                                                  int(max_triangles), counts_ptr or None)
+        return rc == _native.RT_OK
+
+
+def mesh_scratch_bytes(origin, spacing, dims):
+    """rt_terrain_mesh_scratch_bytes: the bytes of extract_mesh_device's scratch block for a lattice (0 for an
+    invalid lattice or one without cells)."""
+    lat = lattice(origin, spacing, dims)
+    return int(lib().rt_terrain_mesh_scratch_bytes(C.byref(lat)))
+
 
 def field_options(eye=None, normals=False, max_blocks=0):
     """An rt_field_options block: the eye (None: the compute's Eye), RT_FIELD_NORMAL, the grid's cap."""

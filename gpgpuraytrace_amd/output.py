@@ -75,3 +75,20 @@ def bgrx_to_rgb(bgrx):
     """(H, W) uint32 (B, G, R, 0) rows -> (H, W, 3) uint8 RGB."""
     b = np.ascontiguousarray(bgrx, np.uint32).view(np.uint8).reshape(*bgrx.shape, 4)
     return b[..., 2::-1].copy()
+
+
+def write_obj(path, vertices, triangles, normals=None):
+    """A triangle mesh (Terrain.extract_mesh) -> Wavefront OBJ: `v x y z` lines, with normals (nv, 3 or 4: the
+    first three columns) `vn x y z` lines, and faces `f a b c` (or `f a//a b//b c//c`) with 1-based indices.
+    Floats are written with 9 significant digits, which reads back to the same float32."""
+    v = np.asarray(vertices, np.float32).reshape(-1, 3)
+    t = np.asarray(triangles, np.int64).reshape(-1, 3) + 1
+    n = None if normals is None else np.asarray(normals, np.float32).reshape(len(v), -1)[:, :3]
+    with open(path, "w") as f:
+        f.write("# %d vertices, %d triangles\n" % (len(v), len(t)))
+        f.writelines("v %.9g %.9g %.9g\n" % tuple(map(float, p)) for p in v)
+        if n is not None:
+            f.writelines("vn %.9g %.9g %.9g\n" % tuple(map(float, p)) for p in n)
+            f.writelines("f %d//%d %d//%d %d//%d\n" % (a, a, b, b, c, c) for a, b, c in t)
+        else:
+            f.writelines("f %d %d %d\n" % (a, b, c) for a, b, c in t)

@@ -586,7 +586,7 @@ int rt_terrain_shade_rays_device(rt_compute screen_cs, const void* rays_device, 
  *   bound, or with the fail-safe word set.  Either kind of compute.  A query reads no frame state and changes none:
  *   it flushes no deferred frame, invalidates no ahead / fused prepass or captured graph, and uploads the constants
  *   it needs to a copy of its own, so it may run between any two renders.
- * Out of scope: mesh extraction (marching cubes over the volume is the caller's); the fog field (getFog); an eye
+ * Mesh extraction over a lattice is rt_terrain_extract_mesh below.  Out of scope: the fog field (getFog); an eye
  *   per point; a caller-chosen eps for the normal; finite differences between lattice neighbours (the normal is
  *   getNormal's, three more density samples a point). */
 enum { RT_FIELD_NORMAL = 32 };
@@ -608,6 +608,63 @@ int rt_terrain_sample_lattice(rt_compute cs, const rt_lattice* lat, const rt_fie
                               uint32_t* occupancy);
 int rt_terrain_sample_lattice_device(rt_compute cs, const rt_lattice* lat, const rt_field_options* opt,
                                      void* results_device, void* occupancy_device);
+
+/* ---- mesh extraction (ABI 9, additive; no reference counterpart) ----
+ * The terrain's surface inside a lattice as an indexed triangle mesh, extracted on the device by surface nets: a
+ * collision or navigation mesh, an export, a proxy for rasterised LOD.  Only the cells that carry surface come back.
+ * The lattice is an rt_lattice exactly as rt_terrain_sample_lattice reads it; D(ix, iy, iz) is its density and a
+ *   point is inside when D > 0 (the occupancy test).
+ * Cells are (cx, cy, cz) with 0 <= c < n - 1 per axis, cell index (cz (ny - 1) + cy) (nx - 1) + cx.  Corner k of a
+ *   cell has bit 0 = +x, bit 1 = +y, bit 2 = +z.  A cell is ACTIVE when its 8 corners are not all inside and not all
+ *   outside.  A lattice with a dim below 2 has no cells: both counts are 0 and nothing else is written.
+ * Edges: a cell has 12, in this order: 0-3 run along x with (ky, kz) = (0,0) (1,0) (0,1) (1,1); 4-7 along y with
+ *   (kx, kz) in the same pattern; 8-11 along z with (kx, ky) in the same pattern.  An edge from its lower endpoint a to
+ *   its upper endpoint b CROSSES when inside(a) != inside(b).
+ * The vertex of an active cell: for each crossing edge t = d_a / (d_a - d_b) (one IEEE subtract, one correctly
+ *   rounded divide); the crossing's local coordinate is t on the edge's axis and the 0 / 1 corner offsets on the
+ *   other two.  The local vertex l is the float32 sum (from 0) of the crossings' local coordinates in edge order,
+ *   divided (correctly rounded) by the float crossing count; no contraction anywhere.  The world coordinate per axis
+ *   is fmaf((float)c + l, spacing, origin): the inner add is one float32 rounding, the fma one.  Every step is
+ *   monotone, so a vertex lies inside its cell's closed box, exactly, in lattice terms.
+ * Vertices are ordered by ascending cell index.  A vertex is 4 words: x y z and the cell index as uint32 bits.
+ * normals (optional): entry i is float4(getNormal(float4(p_i, d_i)), d_i) with d_i = getDensity(p_i): bit for bit
+ *   what rt_terrain_sample_field with RT_FIELD_NORMAL returns for the vertex positions, with the same eye rule
+ *   (RT_RAYS_EYE).
+ * Faces: take a cell c and an axis a.  The lattice edge from c's corner 0 along a is INTERIOR when c's other two
+ *   coordinates are >= 1.  Every interior crossing edge gives one quad over the vertices of the four cells around
+ *   it; quads are ordered by ascending owning cell c, then axis x, y, z.  With (u, v) the next two axes in cyclic
+ *   order after a -- (y, z) for x, (z, x) for y, (x, y) for z -- the four cells are A = c - u - v, B = c - v, C = c,
+ *   D = c - u.  A lower endpoint that is inside gives the triangles (A, B, C), (A, C, D); one that is outside gives
+ *   (A, D, C), (A, C, B): geometric normals point out of the terrain, towards decreasing density, as getNormal's do.
+ *   A triangle is 3 uint32 vertex indices; triangles 2q and 2q + 1 belong to quad q.  The mesh is open at the
+ *   lattice's boundary.
+ * Non-finite densities give unspecified output; the kernels still end.
+ * counts[0..1] always receive the mesh's FULL vertex and triangle counts.  The first min(count, capacity) entries of
+ *   vertices (4 words each), normals (4 floats each, may be NULL: no normal pass runs) and triangles (3 uint32 each)
+ *   are written and nothing beyond them; a truncated call's arrays are a prefix of the full call's.  A capacity of 0
+ *   with a NULL array is a counting call.
+ * opt is an rt_field_options parsed as for the lattice (RT_RAYS_EYE, max_blocks; RT_FIELD_NORMAL is ignored).
+ * rt_terrain_mesh_scratch_bytes: the device form's scratch block for the lattice (its densities, occupancy words,
+ *   mask words and offsets); 0 for an invalid lattice or one without cells.
+ * rt_terrain_extract_mesh: host arrays; blocking; the density is computed on the device, nothing but the counts
+ *   and the written prefixes is downloaded.
+ * rt_terrain_extract_mesh_device: device arrays (scratch, vertices and normals 16-byte aligned), enqueued on the
+ *   compute's device stream; it allocates nothing and never synchronises the host: the counts stay on the device
+ *   and every later pass reads them there.  RT_ERR_INVALID when scratch_bytes is below
+ *   rt_terrain_mesh_scratch_bytes(lat).
+ * Both: RT_ERR_INVALID for the lattice's and the option block's errors (as rt_terrain_sample_lattice), a NULL
+ *   compute, lattice or counts, a capacity above 0 with a NULL array.  RT_ERR_STATE without texPerm2D bound, or with
+ *   the fail-safe word set.  Either kind of compute.  An extraction reads no frame state and changes none: it flushes
+ *   no deferred frame and invalidates no ahead / fused prepass or captured graph, so it may run between any two
+ *   renders. */
+size_t rt_terrain_mesh_scratch_bytes(const rt_lattice* lat);
+int rt_terrain_extract_mesh(rt_compute cs, const rt_lattice* lat, const rt_field_options* opt, float* vertices,
+                            float* normals, uint32_t max_vertices, uint32_t* triangles, uint32_t max_triangles,
+                            uint32_t counts[2]);
+int rt_terrain_extract_mesh_device(rt_compute cs, const rt_lattice* lat, const rt_field_options* opt,
+                                   void* scratch_device, size_t scratch_bytes, void* vertices_device,
+                                   void* normals_device, uint32_t max_vertices, void* triangles_device,
+                                   uint32_t max_triangles, void* counts_device);
 
 /* ---- diagnostics (primitive-level parity tests; no reference counterpart) ----
  * rt_debug_math: device evaluation of the numeric primitives of DESIGN.md §Numerics
