@@ -126,24 +126,6 @@ void rt_launch_camerarays_batch(const RtLaunch& a);
 void rt_launch_tracescreen(const RtLaunch& a, uint32_t off_x, uint32_t off_y, uint32_t ext_x, uint32_t ext_y,
                            uint32_t tile_first, uint32_t tile_stride);
 
-// A ray query (rt_terrain_trace_rays; camerarays.hlsl:12-21 for rays from memory): n rays packed as
-// ox oy oz _ dx dy dz _ (two float4 each) -> results[n] (float4) and, if set, steps[n] (the march loops'
-// iteration counts), with the launch's landscape, noise tables and constants and `eye` in place of Eye.
-// lpr > 1: one lpr-lane segment per ray in blocks of bs threads (nomadplains; the prepass's pairs: rt_rayquery.h
-// Plan).  lpr == 1: the persistent lane kernel, `blocks` blocks of 1024 threads claiming rays from *counter,
-// which the caller zeroes on the stream before every launch.  false: no such kernel (nothing launched).
-struct RtRayQuery {
-    const float4* rays;
-    float4* results;
-    uint32_t* steps; // may be null
-    uint32_t n;
-    float eye[3];
-    int bs, lpr;
-    uint32_t blocks;
-    uint32_t* counter;
-};
-bool rt_launch_rayquery(const RtLaunch& a, const RtRayQuery& q);
-
 // The march of a surface or shaded query's rays: t_min, t_max, stepmod and max_steps (0: unbounded) hold for every
 // ray; with ray_range the rays' spare words are t_min_i and t_max_i instead.
 struct RtMarchParams {
@@ -152,11 +134,17 @@ struct RtMarchParams {
     bool ray_range;
 };
 
-// A surface query (rt_terrain_trace_surface): the refined march tracescreen runs for its pixels
-// (traceRay with skiprefine off, tracing.hlsl:47-105) and getNormal (:107-116) for the same packed rays ->
-// results[2n] (pd.xyz, pd.w | normal, density; the normal 0 where density <= 0) and, if set, steps[n].  Shapes,
-// grid and counter as RtRayQuery's.
-struct RtSurfQuery {
+// A ray or surface query: n rays packed as ox oy oz _ dx dy dz _ (two float4 each), marched with the launch's
+// landscape, noise tables and constants and `eye` in place of Eye; steps[n], if set, takes the march loops'
+// iteration counts.
+//   A ray query (rt_terrain_trace_rays; `surface` false, `march` unused): camerarays.hlsl:12-21 -> results[n].
+//   A surface query (rt_terrain_trace_surface; `surface` true): the refined march tracescreen runs for its pixels
+//   (traceRay with skiprefine off, tracing.hlsl:47-105) with `march`, and getNormal (:107-116) -> results[2n]
+//   (pd.xyz, pd.w | normal, density; the normal 0 where density <= 0).
+// lpr > 1: one lpr-lane segment per ray in blocks of bs threads (nomadplains; the prepass's pairs: rt_rayquery.h
+// Plan).  lpr == 1: the persistent lane kernel, `blocks` blocks of 1024 threads claiming rays from *counter,
+// which the caller zeroes on the stream before every launch.  false: no such kernel (nothing launched).
+struct RtTraceQuery {
     const float4* rays;
     float4* results;
     uint32_t* steps; // may be null
@@ -165,14 +153,15 @@ struct RtSurfQuery {
     int bs, lpr;
     uint32_t blocks;
     uint32_t* counter;
+    bool surface;
     RtMarchParams march;
 };
-bool rt_launch_surfquery(const RtLaunch& a, const RtSurfQuery& q);
+bool rt_launch_tracequery(const RtLaunch& a, const RtTraceQuery& q);
 
 // A shaded query (rt_terrain_shade_rays): the sample tracescreen.hlsl:16-48 computes (one sample, no AO) for the
 // same packed rays -> results[2n] (colour, pd.w | pd.xyz, density), rgba8[n] and steps[2n] (primary, shadow
 // iterations), each if set; results or rgba8 must be.  The constants (a.consts) carry the query's eye, for the
-// sky.  Parameters as RtSurfQuery's; the lanes shape only (bs 1024), so the counter is required.
+// sky.  Parameters as a surface query's; the lanes shape only (bs 1024), so the counter is required.
 struct RtShadeQuery {
     const float4* rays;
     float4* results; // may be null

@@ -97,6 +97,18 @@ __device__ __forceinline__ Ctx make_ctx(const RtConsts* k, const uint32_t* lds)
     return c;
 }
 
+// A query kernel's context: its LOD eye (nomadplains' octave count, getNormal's eps) is a kernel argument in
+// place of the constant block's Eye -- wave-uniform, and the compute's constants stay as the frame loop left them.
+struct QueryEye {
+    float x, y, z;
+};
+__device__ __forceinline__ Ctx make_ctx(const RtConsts* k, const uint32_t* lds, QueryEye e)
+{
+    Ctx c = make_ctx(k, lds);
+    c.eye = rtm::mk(e.x, e.y, e.z);
+    return c;
+}
+
 // STATS kernels: a lane's noise count (NoiseView::calls) into the frame statistics
 __device__ __forceinline__ void stats_noise(RtStats* stats, uint64_t calls)
 {
@@ -2371,240 +2383,153 @@ bool with_segment(int bs, int lpr, F f)
 } // namespace
 
 // ---------------------------------------------------------------------------
-// Ray queries (rt_terrain_trace_rays): camerarays.hlsl:12-21 for rays read from memory instead of
-// getPixelRay's.  Ray i is two 16-byte loads (ox oy oz _ | dx dy dz _), its result one 16-byte store
-// (+ the loop's iteration count with STEPS).  The LOD eye (nomadplains' octave count reads it) is a
-// kernel argument: wave-uniform, and the compute's constant block stays as the frame loop left it.
+// Ray and surface queries (rt_terrain_trace_rays, rt_terrain_trace_surface): traceRay for rays read from memory
+// instead of getPixelRay's, in two kernel shapes that a policy per family completes.  Ray i is two 16-byte loads
+// (ox oy oz _ | dx dy dz _).  The LOD eye is a kernel argument (QueryEye).
+//   A ray query is camerarays.hlsl:12-21: skiprefine, and the prepass's range, stepmod and no cap as compile-time
+//   constants.  Its result is one 16-byte store.
+//   A surface query is the march tracescreen runs for its pixels (skiprefine off, tracescreen.hlsl:20) and
+//   getNormal (tracing.hlsl:107-116); the march's parameters are kernel arguments, and with RANGE the rays' spare
+//   words are t_min_i and t_max_i.  Its result is two 16-byte stores: pd.xyz, pd.w | normal, density (the normal
+//   0 where density <= 0: no hit).
+// Both store the march loop's iteration count with STEPS.
 namespace {
 
-#ifdef RT_RAYQ_UTIL
-// diagnostic build (scripts/ray_query_bench.py): wave steps and live lanes over them of k_rayquery's waves
-__device__ unsigned long long g_rayq_util[2];
+#ifdef RT_QUERY_UTIL
+// diagnostic build (scripts/*_query_bench.py) of the lane kernels' waves: march steps, live lanes summed over
+// them, visits of the refill point with work beside the refill (a wave's ended lanes' normals together; shading
+// visits in k_shadequery), lanes summed over those (both 0 for ray queries)
+__device__ unsigned long long g_query_util[4];
 #endif
 
+// a ray's march: march_begin's arguments and the distance the march ends at
 struct QueryRay {
     f3 p, dir;
+    float t0, endd;
 };
-__device__ __forceinline__ QueryRay load_query_ray(const float4* __restrict__ rays, uint32_t i)
-{
-    const float4 o = rays[2 * (size_t)i], d = rays[2 * (size_t)i + 1];
-    return QueryRay{rtm::mk(o.x, o.y, o.z), rtm::mk(d.x, d.y, d.z)};
-}
-template <bool STEPS, class M>
-__device__ __forceinline__ void store_query_result(const M& st, float4* __restrict__ out,
-                                                   uint32_t* __restrict__ steps, uint32_t i)
-{
-    RayResult rr = march_result(st);
-    if (rr.density < 0.0f) rr.pd.w = RT_CAMERA_FAR;
-    gstore(out + i, make_float4(rr.pd.x, rr.pd.y, rr.pd.z, rr.pd.w));
-    if constexpr (STEPS) steps[i] = (uint32_t)st.iters;
-}
 
-// Segments (nomadplains, few rays): k_camerarays_group with the ray loaded.  One LPR-lane segment per
-// ray, a static deal: the latency shape of the prepass.
-template <bool STEPS, int BS, int LPR>
-__global__ void __launch_bounds__(BS) k_rayquery_seg(const RtConsts* __restrict__ k,
-                                                      const uint32_t* __restrict__ perm2d,
-                                                      const float4* __restrict__ grad,
-                                                      const float4* __restrict__ rays, float4* __restrict__ out,
-                                                      uint32_t* __restrict__ steps, uint32_t n, float ex, float ey,
-                                                      float ez)
+// A family's policy: SKIPREFINE, a ray's march from its two loads and the query's arguments (Args, the kernels'
+// last parameter before the counter), and the store of an ended ray, `normal` being getNormal.
+struct RayArgs {
+    QueryEye eye;
+};
+template <bool STEPS>
+struct RayPolicy {
+    using Args = RayArgs;
+    static constexpr bool SKIPREFINE = true, NORMAL = false, kSteps = STEPS;
+    static __device__ __forceinline__ QueryRay ray(const Args&, float4 o, float4 d)
+    {
+        return QueryRay{rtm::mk(o.x, o.y, o.z), rtm::mk(d.x, d.y, d.z), RT_CAMERA_NEAR, RT_CAMERA_FAR};
+    }
+    static __device__ __forceinline__ float t_max(const Args&) { return RT_CAMERA_FAR; }
+    static __device__ __forceinline__ float stepmod(const Args&) { return 2.0f; }
+    static __device__ __forceinline__ int max_steps(const Args&) { return 0; }
+    template <class M, class Normal>
+    static __device__ __forceinline__ void store(const M& st, float4* __restrict__ out, uint32_t* __restrict__ steps,
+                                                 uint32_t i, Normal)
+    {
+        RayResult rr = march_result(st);
+        if (rr.density < 0.0f) rr.pd.w = RT_CAMERA_FAR;
+        gstore(out + i, make_float4(rr.pd.x, rr.pd.y, rr.pd.z, rr.pd.w));
+        if constexpr (STEPS) steps[i] = (uint32_t)st.iters;
+    }
+};
+
+// (the shaded queries' arguments too)
+struct SurfArgs {
+    QueryEye eye;
+    float t_min, t_max, stepmod;
+    int max_steps;
+};
+template <bool STEPS, bool RANGE>
+struct SurfPolicy {
+    using Args = SurfArgs;
+    static constexpr bool SKIPREFINE = false, NORMAL = true, kSteps = STEPS;
+    static __device__ __forceinline__ QueryRay ray(const Args& a, float4 o, float4 d)
+    {
+        return QueryRay{rtm::mk(o.x, o.y, o.z), rtm::mk(d.x, d.y, d.z), RANGE ? o.w : a.t_min, RANGE ? d.w : a.t_max};
+    }
+    static __device__ __forceinline__ float t_max(const Args& a) { return a.t_max; }
+    static __device__ __forceinline__ float stepmod(const Args& a) { return a.stepmod; }
+    static __device__ __forceinline__ int max_steps(const Args& a) { return a.max_steps; }
+    template <class M, class Normal>
+    static __device__ __forceinline__ void store(const M& st, float4* __restrict__ out, uint32_t* __restrict__ steps,
+                                                 uint32_t i, Normal normal)
+    {
+        const RayResult rr = march_result(st);
+        f3 nrm = rtm::mk(0.0f, 0.0f, 0.0f);
+        if (rr.density > 0.0f) nrm = normal(f4{rr.pd.x, rr.pd.y, rr.pd.z, rr.density});
+        gstore(out + 2 * (size_t)i, make_float4(rr.pd.x, rr.pd.y, rr.pd.z, rr.pd.w));
+        gstore(out + 2 * (size_t)i + 1, make_float4(nrm.x, nrm.y, nrm.z, rr.density));
+        if constexpr (STEPS) steps[i] = (uint32_t)st.iters;
+    }
+};
+
+// Segments (nomadplains, few rays: a pick is one ray, and on one lane its longest march takes milliseconds):
+// k_camerarays_group with the ray loaded.  One LPR-lane segment per ray, a static deal: the latency shape of the
+// prepass.  The march state is replicated over the segment, so the hit test is segment-uniform: the whole segment
+// takes a surface query's normal, its three taps through density_nomadplains_seg, and lane 0 stores.  That store
+// is spelled out here: through the policy's store the STEPS instantiations took two more VGPRs
+// (profiles/r15/query_fold.md).
+template <class P, int BS, int LPR>
+__global__ void __launch_bounds__(BS) k_query_seg(const RtConsts* __restrict__ k, const uint32_t* __restrict__ perm2d,
+                                                  const float4* __restrict__ grad, const float4* __restrict__ rays,
+                                                  float4* __restrict__ out, uint32_t* __restrict__ steps, uint32_t n,
+                                                  typename P::Args a)
 {
     constexpr int L = RT_NOMADPLAINS;
     __shared__ __attribute__((aligned(16))) uint32_t lds[kNoiseLdsWords];
     load_noise_lds(lds, perm2d, grad, k);
     const uint32_t i = blockIdx.x * (uint32_t)(BS / LPR) + threadIdx.x / (uint32_t)LPR;
     if (i >= n) return; // whole segments leave together
-    Ctx c = make_ctx(k, lds);
-    c.eye = rtm::mk(ex, ey, ez);
+    Ctx c = make_ctx(k, lds, a.eye);
     const uint32_t j = threadIdx.x & (LPR - 1u), base = threadIdx.x & 63u & ~(LPR - 1u);
     const SegOctaves<LPR> g = seg_octaves<LPR>(c, j);
-    const QueryRay r = load_query_ray(rays, i);
+    const QueryRay r = P::ray(a, rays[2 * (size_t)i], rays[2 * (size_t)i + 1]);
+    auto dens = [&](f3 q) {
+        uint32_t used;
+        return density_nomadplains_seg<LPR>(c, g, q, j, base, &used);
+    };
     March<L, false> st;
-    march_begin(c, st, r.p, RT_CAMERA_NEAR, 2.0f, r.dir);
-    while (march_live<L, false, true>(c, st, RT_CAMERA_FAR, 0)) {
-        auto dens = [&](f3 q) {
-            uint32_t used;
-            return density_nomadplains_seg<LPR>(c, g, q, j, base, &used);
-        };
-        march_step_with<L, false, true>(c, st, dens);
+    march_begin(c, st, r.p, r.t0, P::stepmod(a), r.dir);
+    while (march_live<L, false, P::SKIPREFINE>(c, st, r.endd, P::max_steps(a)))
+        march_step_with<L, false, P::SKIPREFINE>(c, st, dens);
+    if constexpr (P::NORMAL) {
+        const RayResult rr = march_result(st);
+        f3 nrm = rtm::mk(0.0f, 0.0f, 0.0f);
+        if (rr.density > 0.0f) nrm = get_normal_with(c, f4{rr.pd.x, rr.pd.y, rr.pd.z, rr.density}, dens);
+        if (j == 0) {
+            gstore(out + 2 * (size_t)i, make_float4(rr.pd.x, rr.pd.y, rr.pd.z, rr.pd.w));
+            gstore(out + 2 * (size_t)i + 1, make_float4(nrm.x, nrm.y, nrm.z, rr.density));
+            if constexpr (P::kSteps) steps[i] = (uint32_t)st.iters;
+        }
+    } else {
+        if (j == 0) P::store(st, out, steps, i, 0);
     }
-    if (j == 0) store_query_result<STEPS>(st, out, steps, i);
 }
 
 // Lanes (every landscape, many rays): persistent, one 1024-thread block per CU with the noise tables in
 // LDS once, one lane per ray.  Rays differ in length by more than 100x, so no static deal: a wave whose
 // live lanes fall to `refill_live` or fewer stores its ended rays, claims as many new ones from the
 // query's counter (one atomic per refill, wave_fetch) and hands them to its idle lanes by rank.  Results
-// go to out[ray], so the order of the claims does not show.
-template <int L, bool STEPS>
-__global__ void __launch_bounds__(1024) k_rayquery(const RtConsts* __restrict__ k, const uint32_t* __restrict__ perm2d,
-                                                   const float4* __restrict__ grad, const float4* __restrict__ rays,
-                                                   float4* __restrict__ out, uint32_t* __restrict__ steps, uint32_t n,
-                                                   float ex, float ey, float ez, uint32_t* __restrict__ counter,
-                                                   uint32_t refill_live)
+// go to out[ray], so the order of the claims does not show.  The ended lanes of a wave evaluate their normals
+// together where their results are stored: at the refill and at the end.
+template <int L, class P>
+__global__ void __launch_bounds__(1024) k_query_lanes(const RtConsts* __restrict__ k, const uint32_t* __restrict__ perm2d,
+                                                      const float4* __restrict__ grad, const float4* __restrict__ rays,
+                                                      float4* __restrict__ out, uint32_t* __restrict__ steps, uint32_t n,
+                                                      typename P::Args a, uint32_t* __restrict__ counter,
+                                                      uint32_t refill_live)
 {
-    // (diagnostic) this wave's march steps, and its live lanes summed over them
-    RT_DIAG_RAYQ_UTIL(uint32_t util_wave = 0, util_lane = 0;)
+    // (diagnostic) this wave's march steps and its live lanes summed over them; its stores of hits, and their lanes
+    RT_DIAG_QUERY_UTIL(uint32_t util_wave = 0, util_lane = 0, util_nwave = 0, util_nlane = 0;)
     __shared__ __attribute__((aligned(16))) uint32_t lds[kNoiseLdsWords];
     load_noise_lds(lds, perm2d, grad, k);
-    Ctx c = make_ctx(k, lds);
-    c.eye = rtm::mk(ex, ey, ez);
-    const uint32_t lane = threadIdx.x & 63u;
-    March<L, false> st{};
-    uint32_t idx = 0;
-    bool has = false, live = false; // has: idx is a ray of the query whose result is not stored yet
-    bool more = true;               // (uniform) the counter has not passed n
-    for (;;) {
-        uint64_t lv = __ballot(live);
-        if (more && (uint32_t)__popcll(lv) <= refill_live) {
-            const uint32_t cnt = 64u - (uint32_t)__popcll(lv); // >= 1: refill_live <= 63
-            const uint32_t first = wave_fetch(counter, lane, cnt);
-            if (!live) {
-                if (has) store_query_result<STEPS>(st, out, steps, idx);
-                idx = first + lane_rank(~lv);
-                has = idx < n;
-                if (has) {
-                    const QueryRay r = load_query_ray(rays, idx);
-                    march_begin(c, st, r.p, RT_CAMERA_NEAR, 2.0f, r.dir);
-                    live = march_live<L, false, true>(c, st, RT_CAMERA_FAR, 0);
-                }
-            }
-            more = first + cnt < n;
-            lv = __ballot(live);
-        }
-        if (!lv) {
-            if (!more) break;
-            continue; // every new ray ended before its first step: claim again
-        }
-        RT_DIAG_RAYQ_UTIL(++util_wave; util_lane += (uint32_t)__popcll(lv);)
-        if (live) {
-            march_step<L, false, true>(c, st);
-            live = march_live<L, false, true>(c, st, RT_CAMERA_FAR, 0);
-        }
-    }
-    if (has) store_query_result<STEPS>(st, out, steps, idx);
-    RT_DIAG_RAYQ_UTIL(if (lane == 0) {
-        atomicAdd(&g_rayq_util[0], (unsigned long long)util_wave);
-        atomicAdd(&g_rayq_util[1], (unsigned long long)util_lane);
-    })
-}
-
-} // namespace
-
-bool rt_launch_rayquery(const RtLaunch& a, const RtRayQuery& q)
-{
-    if (q.n == 0 || q.blocks == 0) return true;
-    if (q.lpr > 1) { // segments
-        if (a.landscape != RT_NOMADPLAINS) return false;
-        return with_segment(q.bs, q.lpr, [&](auto bs_tag, auto lpr_tag) {
-            with_bool(q.steps != nullptr, [&](auto steps_tag) {
-                constexpr int BS = decltype(bs_tag)::value, LPR = decltype(lpr_tag)::value;
-                hipLaunchKernelGGL((k_rayquery_seg<decltype(steps_tag)::value, BS, LPR>), dim3(q.blocks), dim3(BS), 0,
-                                   a.stream, a.consts, a.perm2d, a.grad, q.rays, q.results, q.steps, q.n, q.eye[0],
-                                   q.eye[1], q.eye[2]);
-            });
-        });
-    }
-    // the live-lane count at or below which a wave refills (RT_RAYQ_REFILL; at most 63, so a refill claims >= 1 ray)
-    constexpr uint32_t thr = RT_RAYQ_REFILL < 63 ? RT_RAYQ_REFILL : 63;
-    with_landscape(a, [&](auto l_tag) {
-        with_bool(q.steps != nullptr, [&](auto steps_tag) {
-            hipLaunchKernelGGL((k_rayquery<decltype(l_tag)::value, decltype(steps_tag)::value>), dim3(q.blocks),
-                               dim3(1024), 0, a.stream, a.consts, a.perm2d, a.grad, q.rays, q.results, q.steps, q.n,
-                               q.eye[0], q.eye[1], q.eye[2], q.counter, thr);
-        });
-    });
-    return true;
-}
-
-// ---------------------------------------------------------------------------
-// Surface queries (rt_terrain_trace_surface): the march tracescreen runs for its pixels (traceRay with
-// skiprefine off, tracescreen.hlsl:20) and getNormal (tracing.hlsl:107-116) for rays read from memory, in the
-// two shapes of the ray queries above.  Ray i is the same two 16-byte loads; with RANGE their spare words are
-// t_min_i and t_max_i.  Its result is two 16-byte stores: pd.xyz, pd.w | normal, density (the normal 0 where
-// density <= 0: no hit).
-namespace {
-
-#ifdef RT_SURFQ_UTIL
-// diagnostic build (scripts/surface_query_bench.py) of k_surfquery's waves: march steps, live lanes summed
-// over them, normal evaluations (a wave's ended lanes together), lanes summed over those
-__device__ unsigned long long g_surfq_util[4];
-#endif
-
-struct SurfArgs {
-    float ex, ey, ez;
-    float t_min, t_max, stepmod;
-    int max_steps;
-};
-
-template <bool STEPS, class M, class Normal>
-__device__ __forceinline__ void store_surface_result(const M& st, float4* __restrict__ out,
-                                                     uint32_t* __restrict__ steps, uint32_t i, Normal normal)
-{
-    const RayResult rr = march_result(st);
-    f3 nrm = rtm::mk(0.0f, 0.0f, 0.0f);
-    if (rr.density > 0.0f) nrm = normal(f4{rr.pd.x, rr.pd.y, rr.pd.z, rr.density});
-    gstore(out + 2 * (size_t)i, make_float4(rr.pd.x, rr.pd.y, rr.pd.z, rr.pd.w));
-    gstore(out + 2 * (size_t)i + 1, make_float4(nrm.x, nrm.y, nrm.z, rr.density));
-    if constexpr (STEPS) steps[i] = (uint32_t)st.iters;
-}
-
-// Segments (nomadplains, few rays: a pick is one ray, and on one lane its longest march takes milliseconds):
-// k_rayquery_seg's shape.  The march state is replicated over the segment, so the hit test is segment-uniform
-// and the whole segment takes the normal's three taps through density_nomadplains_seg.
-template <bool STEPS, bool RANGE, int BS, int LPR>
-__global__ void __launch_bounds__(BS) k_surfquery_seg(const RtConsts* __restrict__ k,
-                                                       const uint32_t* __restrict__ perm2d,
-                                                       const float4* __restrict__ grad,
-                                                       const float4* __restrict__ rays, float4* __restrict__ out,
-                                                       uint32_t* __restrict__ steps, uint32_t n, SurfArgs a)
-{
-    constexpr int L = RT_NOMADPLAINS;
-    __shared__ __attribute__((aligned(16))) uint32_t lds[kNoiseLdsWords];
-    load_noise_lds(lds, perm2d, grad, k);
-    const uint32_t i = blockIdx.x * (uint32_t)(BS / LPR) + threadIdx.x / (uint32_t)LPR;
-    if (i >= n) return; // whole segments leave together
-    Ctx c = make_ctx(k, lds);
-    c.eye = rtm::mk(a.ex, a.ey, a.ez);
-    const uint32_t j = threadIdx.x & (LPR - 1u), base = threadIdx.x & 63u & ~(LPR - 1u);
-    const SegOctaves<LPR> g = seg_octaves<LPR>(c, j);
-    const float4 o = rays[2 * (size_t)i], d = rays[2 * (size_t)i + 1];
-    const float t0 = RANGE ? o.w : a.t_min, endd = RANGE ? d.w : a.t_max;
-    auto dens = [&](f3 q) {
-        uint32_t used;
-        return density_nomadplains_seg<LPR>(c, g, q, j, base, &used);
-    };
-    March<L, false> st;
-    march_begin(c, st, rtm::mk(o.x, o.y, o.z), t0, a.stepmod, rtm::mk(d.x, d.y, d.z));
-    while (march_live<L, false, false>(c, st, endd, a.max_steps)) march_step_with<L, false, false>(c, st, dens);
-    const RayResult rr = march_result(st);
-    f3 nrm = rtm::mk(0.0f, 0.0f, 0.0f);
-    if (rr.density > 0.0f) nrm = get_normal_with(c, f4{rr.pd.x, rr.pd.y, rr.pd.z, rr.density}, dens);
-    if (j == 0) {
-        gstore(out + 2 * (size_t)i, make_float4(rr.pd.x, rr.pd.y, rr.pd.z, rr.pd.w));
-        gstore(out + 2 * (size_t)i + 1, make_float4(nrm.x, nrm.y, nrm.z, rr.density));
-        if constexpr (STEPS) steps[i] = (uint32_t)st.iters;
-    }
-}
-
-// Lanes (every landscape, many rays): k_rayquery's persistent grid and refill.  The ended lanes of a wave
-// evaluate their normals together where their results are stored: at the refill and at the end.
-template <int L, bool STEPS, bool RANGE>
-__global__ void __launch_bounds__(1024) k_surfquery(const RtConsts* __restrict__ k, const uint32_t* __restrict__ perm2d,
-                                                    const float4* __restrict__ grad, const float4* __restrict__ rays,
-                                                    float4* __restrict__ out, uint32_t* __restrict__ steps, uint32_t n,
-                                                    SurfArgs a, uint32_t* __restrict__ counter, uint32_t refill_live)
-{
-    RT_DIAG_SURFQ_UTIL(uint32_t util_wave = 0, util_lane = 0, util_nwave = 0, util_nlane = 0;)
-    __shared__ __attribute__((aligned(16))) uint32_t lds[kNoiseLdsWords];
-    load_noise_lds(lds, perm2d, grad, k);
-    Ctx c = make_ctx(k, lds);
-    c.eye = rtm::mk(a.ex, a.ey, a.ez);
+    Ctx c = make_ctx(k, lds, a.eye);
     const uint32_t lane = threadIdx.x & 63u;
     auto normal = [&](f4 pd) { return get_normal<L>(c, pd); };
     March<L, false> st{};
-    float endd = a.t_max; // per lane with RANGE
+    float endd = P::t_max(a); // per lane where the rays carry their ranges
     uint32_t idx = 0;
     bool has = false, live = false; // has: idx is a ray of the query whose result is not stored yet
     bool more = true;               // (uniform) the counter has not passed n
@@ -2613,19 +2538,19 @@ __global__ void __launch_bounds__(1024) k_surfquery(const RtConsts* __restrict__
         if (more && (uint32_t)__popcll(lv) <= refill_live) {
             const uint32_t cnt = 64u - (uint32_t)__popcll(lv); // >= 1: refill_live <= 63
             const uint32_t first = wave_fetch(counter, lane, cnt);
-            RT_DIAG_SURFQ_UTIL(if (const uint64_t nm = __ballot(!live && has && st.d > 0.0f)) {
+            RT_DIAG_QUERY_UTIL(if (const uint64_t nm = __ballot(!live && has && st.d > 0.0f); P::NORMAL && nm) {
                 ++util_nwave;
                 util_nlane += (uint32_t)__popcll(nm);
             })
             if (!live) {
-                if (has) store_surface_result<STEPS>(st, out, steps, idx, normal);
+                if (has) P::store(st, out, steps, idx, normal);
                 idx = first + lane_rank(~lv);
                 has = idx < n;
                 if (has) {
-                    const float4 o = rays[2 * (size_t)idx], d = rays[2 * (size_t)idx + 1];
-                    if constexpr (RANGE) endd = d.w;
-                    march_begin(c, st, rtm::mk(o.x, o.y, o.z), RANGE ? o.w : a.t_min, a.stepmod, rtm::mk(d.x, d.y, d.z));
-                    live = march_live<L, false, false>(c, st, endd, a.max_steps);
+                    const QueryRay r = P::ray(a, rays[2 * (size_t)idx], rays[2 * (size_t)idx + 1]);
+                    endd = r.endd;
+                    march_begin(c, st, r.p, r.t0, P::stepmod(a), r.dir);
+                    live = march_live<L, false, P::SKIPREFINE>(c, st, endd, P::max_steps(a));
                 }
             }
             more = first + cnt < n;
@@ -2635,29 +2560,29 @@ __global__ void __launch_bounds__(1024) k_surfquery(const RtConsts* __restrict__
             if (!more) break;
             continue; // every new ray ended before its first step: claim again
         }
-        RT_DIAG_SURFQ_UTIL(++util_wave; util_lane += (uint32_t)__popcll(lv);)
+        RT_DIAG_QUERY_UTIL(++util_wave; util_lane += (uint32_t)__popcll(lv);)
         if (live) {
-            march_step<L, false, false>(c, st);
-            live = march_live<L, false, false>(c, st, endd, a.max_steps);
+            march_step<L, false, P::SKIPREFINE>(c, st);
+            live = march_live<L, false, P::SKIPREFINE>(c, st, endd, P::max_steps(a));
         }
     }
-    RT_DIAG_SURFQ_UTIL(if (const uint64_t nm = __ballot(has && st.d > 0.0f)) {
+    RT_DIAG_QUERY_UTIL(if (const uint64_t nm = __ballot(has && st.d > 0.0f); P::NORMAL && nm) {
         ++util_nwave;
         util_nlane += (uint32_t)__popcll(nm);
     })
-    if (has) store_surface_result<STEPS>(st, out, steps, idx, normal);
-    RT_DIAG_SURFQ_UTIL(if (lane == 0) {
-        atomicAdd(&g_surfq_util[0], (unsigned long long)util_wave);
-        atomicAdd(&g_surfq_util[1], (unsigned long long)util_lane);
-        atomicAdd(&g_surfq_util[2], (unsigned long long)util_nwave);
-        atomicAdd(&g_surfq_util[3], (unsigned long long)util_nlane);
+    if (has) P::store(st, out, steps, idx, normal);
+    RT_DIAG_QUERY_UTIL(if (lane == 0) {
+        atomicAdd(&g_query_util[0], (unsigned long long)util_wave);
+        atomicAdd(&g_query_util[1], (unsigned long long)util_lane);
+        atomicAdd(&g_query_util[2], (unsigned long long)util_nwave);
+        atomicAdd(&g_query_util[3], (unsigned long long)util_nlane);
     })
 }
 
 // the one place a SurfArgs is built: surface and shaded queries alike
 SurfArgs surf_args(const float eye[3], const RtMarchParams& m)
 {
-    return SurfArgs{eye[0], eye[1], eye[2], m.t_min, m.t_max, m.stepmod, m.max_steps};
+    return SurfArgs{{eye[0], eye[1], eye[2]}, m.t_min, m.t_max, m.stepmod, m.max_steps};
 }
 
 // f(STEPS, RANGE) as two bool tags
@@ -2667,33 +2592,42 @@ void with_steps_range(bool steps, bool range, F f)
     with_bool(steps, [&](auto steps_tag) { with_bool(range, [&](auto range_tag) { f(steps_tag, range_tag); }); });
 }
 
+// f(P*, P::Args) with the query's policy P (its family, STEPS and RANGE) and arguments
+template <class F>
+void with_policy(const RtTraceQuery& q, F f)
+{
+    with_steps_range(q.steps != nullptr, q.surface && q.march.ray_range, [&](auto steps_tag, auto range_tag) {
+        constexpr bool STEPS = decltype(steps_tag)::value, RANGE = decltype(range_tag)::value;
+        if (q.surface) f((SurfPolicy<STEPS, RANGE>*)nullptr, surf_args(q.eye, q.march));
+        else if constexpr (!RANGE) f((RayPolicy<STEPS>*)nullptr, RayArgs{{q.eye[0], q.eye[1], q.eye[2]}});
+    });
+}
+
 } // namespace
 
-bool rt_launch_surfquery(const RtLaunch& a, const RtSurfQuery& q)
+bool rt_launch_tracequery(const RtLaunch& a, const RtTraceQuery& q)
 {
     if (q.n == 0 || q.blocks == 0) return true;
-    const SurfArgs sa = surf_args(q.eye, q.march);
-    if (q.lpr > 1) { // segments
-        if (a.landscape != RT_NOMADPLAINS) return false;
-        return with_segment(q.bs, q.lpr, [&](auto bs_tag, auto lpr_tag) {
-            with_steps_range(q.steps != nullptr, q.march.ray_range, [&](auto steps_tag, auto range_tag) {
+    if (q.lpr > 1 && a.landscape != RT_NOMADPLAINS) return false;
+    // the live-lane count at or below which a wave refills (RT_RAYQ_REFILL; at most 63, so a refill claims >= 1 ray)
+    constexpr uint32_t thr = RT_RAYQ_REFILL < 63 ? RT_RAYQ_REFILL : 63;
+    bool found = true;
+    with_policy(q, [&](auto* policy, auto args) {
+        using P = std::remove_pointer_t<decltype(policy)>;
+        if (q.lpr > 1) { // segments
+            found = with_segment(q.bs, q.lpr, [&](auto bs_tag, auto lpr_tag) {
                 constexpr int BS = decltype(bs_tag)::value, LPR = decltype(lpr_tag)::value;
-                constexpr bool STEPS = decltype(steps_tag)::value, RANGE = decltype(range_tag)::value;
-                hipLaunchKernelGGL((k_surfquery_seg<STEPS, RANGE, BS, LPR>), dim3(q.blocks), dim3(BS), 0, a.stream,
-                                   a.consts, a.perm2d, a.grad, q.rays, q.results, q.steps, q.n, sa);
+                hipLaunchKernelGGL((k_query_seg<P, BS, LPR>), dim3(q.blocks), dim3(BS), 0, a.stream, a.consts, a.perm2d,
+                                   a.grad, q.rays, q.results, q.steps, q.n, args);
             });
-        });
-    }
-    constexpr uint32_t thr = RT_RAYQ_REFILL < 63 ? RT_RAYQ_REFILL : 63; // as rt_launch_rayquery
-    with_landscape(a, [&](auto l_tag) {
-        with_steps_range(q.steps != nullptr, q.march.ray_range, [&](auto steps_tag, auto range_tag) {
-            constexpr bool STEPS = decltype(steps_tag)::value, RANGE = decltype(range_tag)::value;
-            hipLaunchKernelGGL((k_surfquery<decltype(l_tag)::value, STEPS, RANGE>), dim3(q.blocks), dim3(1024), 0,
-                               a.stream, a.consts, a.perm2d, a.grad, q.rays, q.results, q.steps, q.n, sa, q.counter,
-                               thr);
+            return;
+        }
+        with_landscape(a, [&](auto l_tag) {
+            hipLaunchKernelGGL((k_query_lanes<decltype(l_tag)::value, P>), dim3(q.blocks), dim3(1024), 0, a.stream,
+                               a.consts, a.perm2d, a.grad, q.rays, q.results, q.steps, q.n, args, q.counter, thr);
         });
     });
-    return true;
+    return found;
 }
 
 // ---------------------------------------------------------------------------
@@ -2703,12 +2637,6 @@ bool rt_launch_surfquery(const RtLaunch& a, const RtSurfQuery& q)
 // loads; its result is two 16-byte stores (colour, pd.w | pd.xyz, density), a packed RGBA8 word and two step
 // counts (primary, shadow), each where its pointer is set.
 namespace {
-
-#ifdef RT_SHADEQ_UTIL
-// diagnostic build (scripts/shade_query_bench.py) of k_shadequery's waves: march steps, live lanes summed over
-// them, shading visits (a wave's ended primaries together), lanes summed over those
-__device__ unsigned long long g_shadeq_util[4];
-#endif
 
 template <bool STEPS>
 __device__ __forceinline__ void store_shade_result(float4* __restrict__ out, uint32_t* __restrict__ out8,
@@ -2720,7 +2648,7 @@ __device__ __forceinline__ void store_shade_result(float4* __restrict__ out, uin
     if constexpr (STEPS) steps[2 * (size_t)i + 1] = (uint32_t)shadow_iters;
 }
 
-// Lanes (every landscape): k_surfquery's persistent grid and refill, a lane's ray in one of two marches: PRIMARY
+// Lanes (every landscape): k_query_lanes' persistent grid and refill, a lane's ray in one of two marches: PRIMARY
 // (refining, to the ray's range and the cap) then, for a hit, SHADOW (skiprefine, to 100, no cap).  Both kinds
 // step in the one march_step_with of the loop, skiprefine per lane.  Everything else runs where a wave visits
 // the refill point, for all its lanes that ended a march since the last visit:
@@ -2741,11 +2669,10 @@ __global__ void __launch_bounds__(1024) k_shadequery(const RtConsts* __restrict_
                                                      uint32_t* __restrict__ steps, uint32_t n, SurfArgs a,
                                                      uint32_t* __restrict__ counter, uint32_t refill_live)
 {
-    RT_DIAG_SHADEQ_UTIL(uint32_t util_wave = 0, util_lane = 0, util_swave = 0, util_slane = 0;)
+    RT_DIAG_QUERY_UTIL(uint32_t util_wave = 0, util_lane = 0, util_swave = 0, util_slane = 0;)
     __shared__ __attribute__((aligned(16))) uint32_t lds[kNoiseLdsWords];
     load_noise_lds(lds, perm2d, grad, k);
-    Ctx c = make_ctx(k, lds);
-    c.eye = rtm::mk(a.ex, a.ey, a.ez);
+    Ctx c = make_ctx(k, lds, a.eye);
     const uint32_t lane = threadIdx.x & 63u;
     auto dens = [&](f3 q) { return get_density<L>(c, q); };
     March<L, true> st{};
@@ -2762,7 +2689,7 @@ __global__ void __launch_bounds__(1024) k_shadequery(const RtConsts* __restrict_
         uint64_t lv = __ballot(live);
         if ((uint32_t)__popcll(lv) <= refill_live && (more || __ballot(has && !live))) {
             const bool ended = has && !live;
-            RT_DIAG_SHADEQ_UTIL(if (const uint64_t sm = __ballot(ended && !shadow)) {
+            RT_DIAG_QUERY_UTIL(if (const uint64_t sm = __ballot(ended && !shadow)) {
                 ++util_swave;
                 util_slane += (uint32_t)__popcll(sm);
             })
@@ -2831,17 +2758,17 @@ __global__ void __launch_bounds__(1024) k_shadequery(const RtConsts* __restrict_
             if (!more && !__ballot(has)) break;
             continue; // lanes hold marches that ended before their first step, or there are rays to claim: visit again
         }
-        RT_DIAG_SHADEQ_UTIL(++util_wave; util_lane += (uint32_t)__popcll(lv);)
+        RT_DIAG_QUERY_UTIL(++util_wave; util_lane += (uint32_t)__popcll(lv);)
         if (live) {
             march_step_with<L, true, false>(c, st, dens, shadow);
             live = march_live_skip(c, st, endd, shadow ? 0 : a.max_steps, shadow);
         }
     }
-    RT_DIAG_SHADEQ_UTIL(if (lane == 0) {
-        atomicAdd(&g_shadeq_util[0], (unsigned long long)util_wave);
-        atomicAdd(&g_shadeq_util[1], (unsigned long long)util_lane);
-        atomicAdd(&g_shadeq_util[2], (unsigned long long)util_swave);
-        atomicAdd(&g_shadeq_util[3], (unsigned long long)util_slane);
+    RT_DIAG_QUERY_UTIL(if (lane == 0) {
+        atomicAdd(&g_query_util[0], (unsigned long long)util_wave);
+        atomicAdd(&g_query_util[1], (unsigned long long)util_lane);
+        atomicAdd(&g_query_util[2], (unsigned long long)util_swave);
+        atomicAdd(&g_query_util[3], (unsigned long long)util_slane);
     })
 }
 
@@ -2872,10 +2799,6 @@ bool rt_launch_shadequery(const RtLaunch& a, const RtShadeQuery& q)
 // strides over the work, so the tables are loaded once per block whatever the size of the query.
 namespace {
 
-struct FieldEye {
-    float x, y, z;
-};
-
 template <int L, bool NORMAL>
 __device__ __forceinline__ void store_field_result(const Ctx& c, f3 p, float d, void* __restrict__ out, uint32_t i)
 {
@@ -2893,12 +2816,11 @@ template <int L, bool NORMAL>
 __global__ void __launch_bounds__(1024) k_fieldpoints(const RtConsts* __restrict__ k, const uint32_t* __restrict__ perm2d,
                                                       const float4* __restrict__ grad,
                                                       const float4* __restrict__ points, void* __restrict__ out,
-                                                      uint32_t n, FieldEye e)
+                                                      uint32_t n, QueryEye e)
 {
     __shared__ __attribute__((aligned(16))) uint32_t lds[kNoiseLdsWords];
     load_noise_lds(lds, perm2d, grad, k);
-    Ctx c = make_ctx(k, lds);
-    c.eye = rtm::mk(e.x, e.y, e.z);
+    Ctx c = make_ctx(k, lds, e);
     const uint32_t tiles = (n + 1023u) / 1024u;
     for (uint32_t t = blockIdx.x; t < tiles; t += gridDim.x) {
         const uint32_t i = t * 1024u + threadIdx.x;
@@ -2924,13 +2846,12 @@ struct FieldLattice {
 template <int L, bool NORMAL, bool COLUMN>
 __global__ void __launch_bounds__(1024) k_fieldlattice(const RtConsts* __restrict__ k, const uint32_t* __restrict__ perm2d,
                                                        const float4* __restrict__ grad, void* __restrict__ out,
-                                                       uint32_t* __restrict__ occ, FieldLattice g, FieldEye e)
+                                                       uint32_t* __restrict__ occ, FieldLattice g, QueryEye e)
 {
     static_assert(!COLUMN || L == RT_NOMADPLAINS, "the column shape is nomadplains'");
     __shared__ __attribute__((aligned(16))) uint32_t lds[kNoiseLdsWords];
     load_noise_lds(lds, perm2d, grad, k);
-    Ctx c = make_ctx(k, lds);
-    c.eye = rtm::mk(e.x, e.y, e.z);
+    Ctx c = make_ctx(k, lds, e);
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
     const uint32_t xc = (g.nx + 63u) / 64u, yc = (g.ny + g.rows - 1u) / g.rows, strips = xc * yc * g.nz;
     const uint32_t words = (g.nx + 31u) / 32u; // occupancy words per (iy, iz) row
@@ -2964,7 +2885,7 @@ __global__ void __launch_bounds__(1024) k_fieldlattice(const RtConsts* __restric
 template <int L, bool NORMAL>
 void launch_fieldquery(const RtLaunch& a, const RtFieldQuery& q)
 {
-    const FieldEye e{q.eye[0], q.eye[1], q.eye[2]};
+    const QueryEye e{q.eye[0], q.eye[1], q.eye[2]};
     if (q.points) {
         hipLaunchKernelGGL((k_fieldpoints<L, NORMAL>), dim3(q.blocks), dim3(1024), 0, a.stream, a.consts, a.perm2d,
                            a.grad, q.points, q.results, q.n, e);
@@ -3214,12 +3135,11 @@ __global__ void __launch_bounds__(1024) k_meshnormals(const RtConsts* __restrict
                                                       const float4* __restrict__ grad,
                                                       const float4* __restrict__ vertices, float4* __restrict__ out,
                                                       const uint32_t* __restrict__ counts, uint32_t max_vertices,
-                                                      FieldEye e)
+                                                      QueryEye e)
 {
     __shared__ __attribute__((aligned(16))) uint32_t lds[kNoiseLdsWords];
     load_noise_lds(lds, perm2d, grad, k);
-    Ctx c = make_ctx(k, lds);
-    c.eye = rtm::mk(e.x, e.y, e.z);
+    Ctx c = make_ctx(k, lds, e);
     const uint32_t have = counts[0], n = have < max_vertices ? have : max_vertices;
     const uint32_t tiles = (n + 1023u) / 1024u;
     for (uint32_t t = blockIdx.x; t < tiles; t += gridDim.x) {
@@ -3249,7 +3169,7 @@ bool rt_launch_meshquery(const RtLaunch& a, const RtMeshQuery& q)
         hipLaunchKernelGGL(k_meshemit, dim3(q.emit_blocks), dim3(rtq::kMeshThreads), 0, a.stream, q.density, q.masks, offsets, g,
                            q.vertices, q.max_vertices, q.triangles, q.max_triangles);
     if (q.normals && q.max_vertices) {
-        const FieldEye e{q.eye[0], q.eye[1], q.eye[2]};
+        const QueryEye e{q.eye[0], q.eye[1], q.eye[2]};
         with_landscape(a, [&](auto l_tag) {
             hipLaunchKernelGGL((k_meshnormals<decltype(l_tag)::value>), dim3(q.normal_blocks), dim3(1024), 0, a.stream,
                                a.consts, a.perm2d, a.grad, q.vertices, q.normals, q.counts, q.max_vertices, e);
@@ -3409,45 +3329,16 @@ extern "C" int rt_debug_live_hist(unsigned long long* out, int reset)
 }
 #endif
 
-#ifdef RT_RAYQ_UTIL
-// diagnostic build: copies (and with reset != 0 clears) k_rayquery's (wave steps, live lanes summed over them)
-extern "C" int rt_debug_rayquery_util(unsigned long long* out, int reset)
+#ifdef RT_QUERY_UTIL
+// diagnostic build: copies (and with reset != 0 clears) the query lane kernels' g_query_util, summed over the
+// launches since the last reset
+extern "C" int rt_debug_query_util(unsigned long long* out, int reset)
 {
     if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_rayq_util), 16) != hipSuccess) return -1;
-    if (reset) {
-        static const unsigned long long zero[2] = {};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_rayq_util), zero, 16) != hipSuccess) return -1;
-    }
-    return 2;
-}
-#endif
-
-#ifdef RT_SURFQ_UTIL
-// diagnostic build: copies (and with reset != 0 clears) k_surfquery's (wave steps, live lanes summed over them,
-// normal evaluations, lanes summed over those)
-extern "C" int rt_debug_surfquery_util(unsigned long long* out, int reset)
-{
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_surfq_util), 32) != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_query_util), 32) != hipSuccess) return -1;
     if (reset) {
         static const unsigned long long zero[4] = {};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_surfq_util), zero, 32) != hipSuccess) return -1;
-    }
-    return 4;
-}
-#endif
-
-#ifdef RT_SHADEQ_UTIL
-// diagnostic build: copies (and with reset != 0 clears) k_shadequery's (wave steps, live lanes summed over them,
-// shading visits, lanes summed over those)
-extern "C" int rt_debug_shadequery_util(unsigned long long* out, int reset)
-{
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_shadeq_util), 32) != hipSuccess) return -1;
-    if (reset) {
-        static const unsigned long long zero[4] = {};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_shadeq_util), zero, 32) != hipSuccess) return -1;
+        if (hipMemcpyToSymbol(HIP_SYMBOL(g_query_util), zero, 32) != hipSuccess) return -1;
     }
     return 4;
 }

@@ -145,7 +145,7 @@ struct rt_device_s {
     uint32_t* gate = nullptr;  // the gated launch (GatedPrepass): per frame task flags + ray counter
     uint32_t* claims = nullptr; //   and the units claimed per tile of the batch's order
     uint32_t* aocc = nullptr;
-    uint32_t* rq_counter = nullptr; // the ray queries' claim counter (k_rayquery), zeroed on the stream per call
+    uint32_t* rq_counter = nullptr; // the ray queries' claim counter (k_query_lanes), zeroed on the stream per call
     size_t samples_cap = 0;
     // dominant-kernel timing (rt_device_set_profiling)
     bool profiling = false;
@@ -2995,7 +2995,7 @@ int trace_rays_enqueue(rt_compute c, const void* rays_device, uint32_t n, const 
 {
     rt_device dev = c->dev;
     RtLaunch a;
-    RtRayQuery q{};
+    RtTraceQuery q{};
     if (int rc = query_prepare(c, o, false, &a, q.eye)) return rc;
     rtq::Plan p;
     const char* why = "";
@@ -3011,7 +3011,7 @@ int trace_rays_enqueue(rt_compute c, const void* rays_device, uint32_t n, const 
     q.blocks = p.blocks;
     if (p.shape == rtq::LANES)
         if (int rc = arm_counter(dev, &q.counter)) return rc;
-    return query_launched(rt_launch_rayquery(a, q), "rt_terrain_trace_rays: no kernel for this shape");
+    return query_launched(rt_launch_tracequery(a, q), "rt_terrain_trace_rays: no kernel for this shape");
 }
 
 const QueryFamily<rtq::Options> kRayFamily{"rt_terrain_trace_rays", "ray", rtq::parse_options};
@@ -3057,7 +3057,7 @@ int trace_surface_enqueue(rt_compute c, const void* rays_device, uint32_t n, con
 {
     rt_device dev = c->dev;
     RtLaunch a;
-    RtSurfQuery q{};
+    RtTraceQuery q{};
     if (int rc = query_prepare(c, o, false, &a, q.eye)) return rc;
     rtq::Plan p;
     const char* why = "";
@@ -3071,10 +3071,11 @@ int trace_surface_enqueue(rt_compute c, const void* rays_device, uint32_t n, con
     q.bs = p.bs;
     q.lpr = p.lpr;
     q.blocks = p.blocks;
+    q.surface = true;
     q.march = march_params(o);
     if (p.shape == rtq::LANES)
         if (int rc = arm_counter(dev, &q.counter)) return rc;
-    return query_launched(rt_launch_surfquery(a, q), "rt_terrain_trace_surface: no kernel for this shape");
+    return query_launched(rt_launch_tracequery(a, q), "rt_terrain_trace_surface: no kernel for this shape");
 }
 
 const QueryFamily<rtq::SurfOptions> kSurfFamily{"rt_terrain_trace_surface", "ray", rtq::parse_surface_options};

@@ -96,7 +96,7 @@
 #define RT_PREPASS_LPR1 16
 #endif
 
-// k_rayquery (the ray queries' lane shape): a wave refills its idle lanes from the query's counter once its live
+// k_query_lanes (the ray and surface queries' lane shape): a wave refills its idle lanes from the query's counter once its live
 // lanes are this many or fewer (0: only when all have ended; 63: as soon as one ends).  A refill is one atomic
 // round trip the wave waits for.  2^20 nomadplains rays, ms per query (lane utilisation over the march steps), in
 // grid order / shuffled: 0: 5.37 (95%) / 9.18 (47%), 32: 6.33 / 8.66, 48: 5.84 (92%) / 8.26 (71%), 56: 5.77 (94%)
@@ -113,7 +113,7 @@
 // (normal, colour FBM, sky) runs on more lanes a visit, and the march on fewer.  The 2,073,600 pixel rays of the
 // 1920x1080 reset-pose frame, ms per query (lane utilisation of the march steps / of the shading visits): 56: 4.98
 // (80% / 13%), 48: 4.47 (78% / 20%), 40: 4.31 (76% / 28%), 32: 4.20 (71% / 35%), 24: 4.23 (68% / 44%), spreads 1-3%
-// (profiles/r11/shade_query.md).  k_rayquery's 56 leaves 8 lanes a visit for work worth several march steps.
+// (profiles/r11/shade_query.md).  k_query_lanes' 56 leaves 8 lanes a visit for work worth several march steps.
 #ifndef RT_SHADEQ_REFILL
 #define RT_SHADEQ_REFILL 32
 #endif
@@ -145,8 +145,8 @@
 // RT_WAVE_TRACE          per-wave timeline of k_trace (make trace; scripts/wave_trace.py); fields 23-27: segment-job
 //                        time / jobs / loop steps, lane-refill long-ray loop steps / time
 // RT_LIVE_HIST           histogram of live lanes per primary march step (rt_debug_live_hist)
-// RT_RAYQ_UTIL / RT_SURFQ_UTIL / RT_SHADEQ_UTIL  lane utilisation of the query kernels' waves
-//                        (rt_debug_rayquery_util / _surfquery_util / _shadequery_util; scripts/*_query_bench.py)
+// RT_QUERY_UTIL          lane utilisation of the ray, surface and shaded queries' lane kernels' waves
+//                        (rt_debug_query_util; scripts/*_query_bench.py)
 // RT_COUNT_PRIMARY_STEPS count live lanes per primary march step as noise (scripts/phase_util.py)
 // RT_COUNT_LONG_STEPS=k  the same for long-ray steps (1 always, 2 after the drain, 3 before)
 // RT_COUNT_PHASE=k       count only the noise of k_trace work kind k (rt_shader.h count_noise)
@@ -173,20 +173,10 @@
 #else
 #define RT_DIAG_LIVE_HIST(...)
 #endif
-#ifdef RT_RAYQ_UTIL
-#define RT_DIAG_RAYQ_UTIL(...) __VA_ARGS__
+#ifdef RT_QUERY_UTIL
+#define RT_DIAG_QUERY_UTIL(...) __VA_ARGS__
 #else
-#define RT_DIAG_RAYQ_UTIL(...)
-#endif
-#ifdef RT_SURFQ_UTIL
-#define RT_DIAG_SURFQ_UTIL(...) __VA_ARGS__
-#else
-#define RT_DIAG_SURFQ_UTIL(...)
-#endif
-#ifdef RT_SHADEQ_UTIL
-#define RT_DIAG_SHADEQ_UTIL(...) __VA_ARGS__
-#else
-#define RT_DIAG_SHADEQ_UTIL(...)
+#define RT_DIAG_QUERY_UTIL(...)
 #endif
 #ifdef RT_COUNT_PRIMARY_STEPS
 #define RT_DIAG_PRIMARY_STEPS(...) __VA_ARGS__

@@ -7,13 +7,14 @@
         2. both forced shapes at n = 1 .. 2^20 on nomadplains (the auto rule's crossing);
         3. n = 2^20 on every landscape, in rays/s.
     RT_LIB_VARIANT=rqN python3 scripts/ray_query_bench.py util OUT_DIR
-        a build with -DRT_RAYQ_UTIL -DRT_RAYQ_REFILL=N (make variant): time and lane utilisation of the lane shape
+        a build with -DRT_QUERY_UTIL -DRT_RAYQ_REFILL=N (make variant): time and lane utilisation of the lane shape
         at n = 2^20 on nomadplains, the rays in grid order and under a seeded permutation; appends one JSON line
         each to OUT_DIR/ray_query_util.jsonl.
 
 The device form on the device's stream, HIP events around R back-to-back launches (R sized so that a window lasts
 >= 50 ms), every shape warmed up first, 5 repeats per pair with the two sides alternating; the spread of a side is
-(max - min) / median of its repeats.  --resources embeds scripts/resource_usage.py's lines for k_rayquery*."""
+(max - min) / median of its repeats.  --resources embeds scripts/resource_usage.py's lines for the ray queries'
+kernels."""
 import json
 import math
 import os
@@ -200,7 +201,7 @@ def throughput3(out):
 
 def util(out_dir):
     L = G.lib()
-    L.rt_debug_rayquery_util.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
+    L.rt_debug_query_util.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
     n = 1 << 20
     o, d = grid_rays(n)
     perm = np.random.default_rng(20).permutation(n)
@@ -212,11 +213,11 @@ def util(out_dir):
         q = Query(ter, oo, dd, RF.eye("F0"), "lanes")
         r = reps_for(stream, q)
         s = summary([timed(stream, q, r) for _ in range(REPEATS)])
-        buf = (C.c_ulonglong * 2)()
-        assert L.rt_debug_rayquery_util(buf, 1) == 2
+        buf = (C.c_ulonglong * 4)()  # (slots 2 and 3 stay 0: no normals)
+        assert L.rt_debug_query_util(buf, 1) == 4
         q()
         dev.synchronize()
-        assert L.rt_debug_rayquery_util(buf, 1) == 2
+        assert L.rt_debug_query_util(buf, 1) == 4
         s.update({"variant": os.environ.get("RT_LIB_VARIANT", ""), "order": order, "wave_steps": int(buf[0]),
                   "lane_steps": int(buf[1]), "utilisation": buf[1] / (64.0 * buf[0])})
         print(json.dumps(s), flush=True)
@@ -268,7 +269,8 @@ if __name__ == "__main__":
     else:
         res = []
         if "--resources" in sys.argv:
-            res = [ln.rstrip() for ln in open(sys.argv[sys.argv.index("--resources") + 1]) if "k_rayquery" in ln]
+            res = [ln.rstrip() for ln in open(sys.argv[sys.argv.index("--resources") + 1])
+                   if "k_query" in ln and "RayPolicy" in ln]
         out = {}
         bar1(out)
         table2(out)

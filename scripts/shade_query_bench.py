@@ -9,7 +9,7 @@
         pixels that equal the frame's (the rays are formed in numpy, so a few differ in the last bit of a
         direction), and the query's march iterations from its own step counts.
     RT_LIB_VARIANT=NAME python3 scripts/shade_query_bench.py util OUT_DIR
-        a build with -DRT_SHADEQ_UTIL (make variant): lane utilisation of k_shadequery's march steps and of its
+        a build with -DRT_QUERY_UTIL (make variant): lane utilisation of k_shadequery's march steps and of its
         shading visits for the largest query; appends one JSON line to OUT_DIR/shade_query_util.jsonl.
 
 Timing as ray_query_bench.py: the device form on the device's stream, HIP events around back-to-back launches of
@@ -141,16 +141,16 @@ def bars(out):
 
 def util(out_dir):
     L = G.lib()
-    L.rt_debug_shadequery_util.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
+    L.rt_debug_query_util.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
     dev, ter, cam = frame_terrain()
     stream = torch.cuda.ExternalStream(dev.stream(), device="cuda:0")
     q, _ = frame_query(dev, ter, cam)
     s = RQ.summary([RQ.timed(stream, q, RQ.reps_for(stream, q)) for _ in range(RQ.REPEATS)])
     buf = (C.c_ulonglong * 4)()
-    assert L.rt_debug_shadequery_util(buf, 1) == 4
+    assert L.rt_debug_query_util(buf, 1) == 4
     q()
     dev.synchronize()
-    assert L.rt_debug_shadequery_util(buf, 1) == 4
+    assert L.rt_debug_query_util(buf, 1) == 4
     s.update({"variant": os.environ.get("RT_LIB_VARIANT", ""), "n": q.n, "wave_steps": int(buf[0]), "lane_steps": int(buf[1]),
               "shading_visits": int(buf[2]), "shading_lanes": int(buf[3]),
               "march_utilisation": buf[1] / (64.0 * max(buf[0], 1)),

@@ -9,7 +9,7 @@
         2. both forced shapes by n (the auto rule's crossing);
         3. one pick (n = 1, segments) in microseconds.
     RT_LIB_VARIANT=NAME python3 scripts/surface_query_bench.py util OUT_DIR
-        a build with -DRT_SURFQ_UTIL (make variant): lane utilisation of the lane shape's march steps and of its
+        a build with -DRT_QUERY_UTIL (make variant): lane utilisation of the lane shape's march steps and of its
         normal evaluations at n = 2^20; appends one JSON line to OUT_DIR/surface_query_util.jsonl.
 
 Rays: F0's 1024 prepass rays (tests/ray_fixture.py) with their origins moved over a 32 x 32 grid of pitch 8 and
@@ -120,7 +120,7 @@ def bars(out):
 
 def util(out_dir):
     L = G.lib()
-    L.rt_debug_surfquery_util.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
+    L.rt_debug_query_util.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
     n = 1 << 20
     o, d = shifted_rays(n)
     dev, ter = RQ.terrain("nomadplains")
@@ -129,10 +129,10 @@ def util(out_dir):
     r = RQ.reps_for(stream, q)
     s = RQ.summary([RQ.timed(stream, q, r) for _ in range(RQ.REPEATS)])
     buf = (C.c_ulonglong * 4)()
-    assert L.rt_debug_surfquery_util(buf, 1) == 4
+    assert L.rt_debug_query_util(buf, 1) == 4
     q()
     dev.synchronize()
-    assert L.rt_debug_surfquery_util(buf, 1) == 4
+    assert L.rt_debug_query_util(buf, 1) == 4
     s.update({"variant": os.environ.get("RT_LIB_VARIANT", ""), "wave_steps": int(buf[0]), "lane_steps": int(buf[1]),
               "normal_wave_calls": int(buf[2]), "normal_lanes": int(buf[3]),
               "march_utilisation": buf[1] / (64.0 * max(buf[0], 1)),
@@ -165,7 +165,7 @@ def markdown(out, resources):
     big = out["main"][-1]["lanes"]
     ratio = big["surface"]["ns_per_iteration"] / big["trace_rays"]["ns_per_iteration"]
     out["lanes_ns_per_iteration_ratio_2p20"] = ratio
-    lines += ["", "Lanes at 2^20 rays: the surface query's time per iteration is %.3f x k_rayquery's." % ratio, "",
+    lines += ["", "Lanes at 2^20 rays: the surface query's time per iteration is %.3f x the ray query's." % ratio, "",
               "## 2. Both shapes by n (the auto rule's crossing)", "",
               "| n | segments ms | lanes ms | faster |", "|---|---|---|---|"]
     for r in out["crossing"]:
@@ -191,7 +191,8 @@ if __name__ == "__main__":
     else:
         res = []
         if "--resources" in sys.argv:
-            res = [ln.rstrip() for ln in open(sys.argv[sys.argv.index("--resources") + 1]) if "k_surfquery" in ln]
+            res = [ln.rstrip() for ln in open(sys.argv[sys.argv.index("--resources") + 1])
+                   if "k_query" in ln and "SurfPolicy" in ln]
         out = {}
         bars(out)
         md = markdown(out, res)
