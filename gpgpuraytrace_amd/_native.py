@@ -55,6 +55,14 @@ class RtSurfaceOptions(C.Structure):
                 ("t_min", C.c_float), ("t_max", C.c_float), ("stepmod", C.c_float), ("max_steps", C.c_uint32)]
 
 
+RT_POINT_MAX_AO = 16  # rt_point_options.ao_samples: ao_dir packs the AO ray's index into 4 bits
+
+
+class RtPointOptions(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("eye", C.c_float * 3), ("max_blocks", C.c_uint32),
+                ("ao_samples", C.c_uint32), ("seed", C.c_uint32)]
+
+
 RT_FIELD_NORMAL = 32  # rt_field_options.flags beside RT_RAYS_EYE: results are float4 {normal, density}
 RT_MAX_LATTICE_DIM = 4096
 
@@ -149,6 +157,10 @@ SIGNATURES = {
     # shaded queries (one sample a ray, no AO): the tracescreen compute; results (8n floats), rgba8 (n), steps (2n)
     "rt_terrain_shade_rays": (_i, [_vp, _vp, _vp, _vp, _i, C.POINTER(RtSurfaceOptions), _vp, _vp, _vp]),
     "rt_terrain_shade_rays_device": (_i, [_vp, _vp, _i, C.POINTER(RtSurfaceOptions), _vp, _vp, _vp]),
+    # point shading: colour, sun shadow and AO at points with normals (n x 3 host, n x 4 device); the tracescreen
+    # compute; results (4n floats), rgba8 (n), steps (2n)
+    "rt_terrain_shade_points": (_i, [_vp, _vp, _vp, _i, C.POINTER(RtPointOptions), _vp, _vp, _vp]),
+    "rt_terrain_shade_points_device": (_i, [_vp, _vp, _vp, _i, C.POINTER(RtPointOptions), _vp, _vp, _vp]),
     # field queries: density (and normal) at points (n x 3 host, n x 4 device) and on a lattice (+ occupancy bits)
     "rt_terrain_sample_field": (_i, [_vp, _vp, _i, C.POINTER(RtFieldOptions), _vp]),
     "rt_terrain_sample_field_device": (_i, [_vp, _vp, _i, C.POINTER(RtFieldOptions), _vp]),

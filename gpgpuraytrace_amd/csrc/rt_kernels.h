@@ -175,6 +175,26 @@ struct RtShadeQuery {
 };
 bool rt_launch_shadequery(const RtLaunch& a, const RtShadeQuery& q);
 
+// A point shading query (rt_terrain_shade_points): getColor with its shadow ray and the AO factor of ao_samples
+// (0..16) hemisphere rays hashed from (point index, seed) at n points x y z _ with normals nx ny nz _ (one float4
+// each) -> results[n] (colour, ao), rgba8[n] (ao times the saturated colour) and steps[2n] (shadow iterations, the
+// AO rays' sum), each if set; results or rgba8 must be.  `eye` is in place of Eye and the viewpoint of the
+// colour; the constants are the compute's as they are.  The lanes shape only (bs 1024), so the counter is
+// required.  false: nothing launched.
+struct RtPointQuery {
+    const float4* points;
+    const float4* normals;
+    float4* results; // may be null
+    uint32_t* rgba8; // may be null
+    uint32_t* steps; // may be null
+    uint32_t n;
+    float eye[3];
+    uint32_t ao_samples, seed;
+    uint32_t blocks;
+    uint32_t* counter;
+};
+bool rt_launch_shadepoints(const RtLaunch& a, const RtPointQuery& q);
+
 // A field query (rt_terrain_sample_field / rt_terrain_sample_lattice): getDensity, with `normal` also getNormal
 // (tracing.hlsl:107-116, for every point), with the launch's landscape, noise tables and constants and `eye` in
 // place of Eye.  points set: n points x y z _ (one float4 each) -> results[n], float or with `normal` float4

@@ -2398,7 +2398,8 @@ namespace {
 #ifdef RT_QUERY_UTIL
 // diagnostic build (scripts/*_query_bench.py) of the lane kernels' waves: march steps, live lanes summed over
 // them, visits of the refill point with work beside the refill (a wave's ended lanes' normals together; shading
-// visits in k_shadequery), lanes summed over those (both 0 for ray queries)
+// visits in k_shadequery, visits that claim points in k_shadepoints), lanes summed over those (both 0 for ray
+// queries)
 __device__ unsigned long long g_query_util[4];
 #endif
 
@@ -2786,6 +2787,156 @@ bool rt_launch_shadequery(const RtLaunch& a, const RtShadeQuery& q)
             hipLaunchKernelGGL((k_shadequery<decltype(l_tag)::value, STEPS, RANGE>), dim3(q.blocks), dim3(1024), 0,
                                a.stream, a.consts, a.perm2d, a.grad, q.rays, q.results, q.rgba8, q.steps, q.n, sa,
                                q.counter, thr);
+        });
+    });
+    return true;
+}
+
+// ---------------------------------------------------------------------------
+// Point shading (rt_terrain_shade_points): getColor with its shadow ray and the AO factor of K hemisphere rays at
+// points the caller holds, as a frame computes both for a pixel whose primary ray ended there -- no primary march,
+// no fog or sky blend.  Point i is two 16-byte loads (x y z _ | nx ny nz _); its result is one 16-byte store
+// (colour, ao), a packed RGBA8 word (ao times the saturated colour) and two step counts (shadow, the AO rays'
+// sum), each where its pointer is set.
+namespace {
+
+// (wave-uniform) the LOD eye and viewpoint, the AO rays a point and the hash's py
+struct PointArgs {
+    QueryEye eye;
+    uint32_t ao, seed;
+};
+
+// Lanes (every landscape): k_shadequery's persistent grid and refill, a lane's point in one of 1 + K marches, one
+// after another: SHADOW (to 100, with fog), then AO ray 0 .. K - 1 (to 25, without).  `phase` counts the marches
+// begun after the shadow's: 0 is SHADOW, k + 1 is AO ray k.  All are skiprefine and step in the one
+// march_step_with of the loop.  Everything else runs where a wave visits the refill point, for all its lanes
+// that ended a march since the last visit:
+//   an ended SHADOW: the rest of getColor; the colour takes the place of the albedo in the lane's ShadePre;
+//   an ended AO ray: its occlusion is counted;
+//   either then begins the point's next AO ray, or after the last stores the point;
+//   a lane without a point claims one from the query's counter, takes getColor up to its shadow ray (on
+//     nomadplains the 20-octave colour FBM, so for all the newly claimed lanes together) and begins that ray.
+// A lane carries beside its March the point's ShadePre (the shadow stepmod is the AO rays' too), its normal and
+// the counts; the position is the marches' origin (March::p).
+// The loop ends when the counter has passed n, no lane is live and no lane holds a point: a visit is due whenever
+// the live lanes are few enough and there is something to do (points to claim, or a lane with an ended march), a
+// visit claims at least one point or moves every ended march on by one phase (of 1 + K a point, the last one's
+// end being the store), and a wave with no live lane always visits or leaves.
+template <int L, bool STEPS>
+__global__ void __launch_bounds__(1024) k_shadepoints(const RtConsts* __restrict__ k, const uint32_t* __restrict__ perm2d,
+                                                      const float4* __restrict__ grad, const float4* __restrict__ points,
+                                                      const float4* __restrict__ normals, float4* __restrict__ out,
+                                                      uint32_t* __restrict__ out8, uint32_t* __restrict__ steps,
+                                                      uint32_t n, PointArgs a, uint32_t* __restrict__ counter,
+                                                      uint32_t refill_live)
+{
+    // (diagnostic) this wave's march steps and its live lanes summed over them; its visits that began shadow rays
+    // (the colour's FBM), and their lanes
+    RT_DIAG_QUERY_UTIL(uint32_t util_wave = 0, util_lane = 0, util_swave = 0, util_slane = 0;)
+    __shared__ __attribute__((aligned(16))) uint32_t lds[kNoiseLdsWords];
+    load_noise_lds(lds, perm2d, grad, k);
+    Ctx c = make_ctx(k, lds, a.eye);
+    const uint32_t lane = threadIdx.x & 63u;
+    auto dens = [&](f3 q) { return get_density<L>(c, q); };
+    March<L, true> st{};
+    ShadePre sp{};                       // getColor's terms before its shadow ray; col: the colour once that ray ended
+    f3 nrm = rtm::mk(0.0f, 0.0f, 0.0f); // n_i
+    uint32_t idx = 0, phase = 0, occ = 0;
+    uint32_t it_shadow = 0, it_ao = 0; // (STEPS) the shadow march's iterations, the ended AO marches' sum
+    bool has = false, live = false;    // has: idx is a point of the query whose result is not stored yet
+    bool more = true;                  // (uniform) the counter has not passed n
+    for (;;) {
+        uint64_t lv = __ballot(live);
+        if ((uint32_t)__popcll(lv) <= refill_live && (more || __ballot(has && !live))) {
+            if (has && !live) {
+                if (phase == 0u) { // color.hlsl:53-71 after the shadow ray
+                    const f3 col = shade_post(c, sp, st.d, st.f.w);
+                    sp.col[0] = col.x;
+                    sp.col[1] = col.y;
+                    sp.col[2] = col.z;
+                    if constexpr (STEPS) it_shadow = (uint32_t)st.iters;
+                } else { // ambient_occlusion's count
+                    if (st.d > 0.0f) ++occ;
+                    if constexpr (STEPS) it_ao += (uint32_t)st.iters;
+                }
+                if (phase < a.ao) { // AO ray `phase` (rt_shader.h ao_dir: px = i, py = seed, a = 0)
+                    march_begin(c, st, st.p, 0.4f, sp.precision, ao_dir(nrm, idx, a.seed, 0u, phase), false);
+                    ++phase;
+                    live = march_live<L, true, true>(c, st, RT_AO_END, 0);
+                } else {
+                    const float ao = a.ao ? ao_factor(occ, (int)a.ao) : 1.0f;
+                    if (out) gstore(out + idx, make_float4(sp.col[0], sp.col[1], sp.col[2], ao));
+                    if (out8)
+                        out8[idx] = unorm8(rtm::sat(sp.col[0]) * ao) | (unorm8(rtm::sat(sp.col[1]) * ao) << 8) |
+                                    (unorm8(rtm::sat(sp.col[2]) * ao) << 16) | 0xff000000u;
+                    if constexpr (STEPS) {
+                        steps[2 * (size_t)idx] = it_shadow;
+                        steps[2 * (size_t)idx + 1] = it_ao;
+                    }
+                    has = false;
+                }
+            }
+            if (more) {
+                const uint64_t idle = __ballot(!has);
+                const uint32_t cnt = (uint32_t)__popcll(idle);
+                const uint32_t first = wave_fetch(counter, lane, cnt);
+                bool fresh = false;
+                if (!has) {
+                    idx = first + lane_rank(idle);
+                    has = fresh = idx < n;
+                }
+                RT_DIAG_QUERY_UTIL(if (const uint64_t sm = __ballot(fresh)) {
+                    ++util_swave;
+                    util_slane += (uint32_t)__popcll(sm);
+                })
+                if (fresh) {
+                    const float4 pw = points[idx], nw = normals[idx];
+                    const f3 p = rtm::mk(pw.x, pw.y, pw.z), v = rtm::sub(p, c.eye);
+                    nrm = rtm::mk(nw.x, nw.y, nw.z);
+                    sp = shade_pre<L>(c, p, nrm, rtm::normalize(v), rtm::length(v));
+                    phase = 0u;
+                    occ = 0u;
+                    it_ao = 0u;
+                    // color.hlsl:51 traceRay(p, 0.4, 100, precision, SunDirection, fog, skiprefine)
+                    march_begin(c, st, p, 0.4f, sp.precision, c.sun);
+                    live = march_live<L, true, true>(c, st, 100.0f, 0);
+                }
+                more = first + cnt < n;
+            }
+            lv = __ballot(live);
+        }
+        if (!lv) {
+            if (!more && !__ballot(has)) break;
+            continue; // lanes hold marches that ended before their first step, or there are points to claim: visit again
+        }
+        RT_DIAG_QUERY_UTIL(++util_wave; util_lane += (uint32_t)__popcll(lv);)
+        if (live) {
+            march_step_with<L, true, false>(c, st, dens, /*skiprefine*/ true);
+            live = march_live<L, true, true>(c, st, phase ? RT_AO_END : 100.0f, 0);
+        }
+    }
+    RT_DIAG_QUERY_UTIL(if (lane == 0) {
+        atomicAdd(&g_query_util[0], (unsigned long long)util_wave);
+        atomicAdd(&g_query_util[1], (unsigned long long)util_lane);
+        atomicAdd(&g_query_util[2], (unsigned long long)util_swave);
+        atomicAdd(&g_query_util[3], (unsigned long long)util_slane);
+    })
+}
+
+} // namespace
+
+bool rt_launch_shadepoints(const RtLaunch& a, const RtPointQuery& q)
+{
+    if (q.n == 0 || q.blocks == 0) return true;
+    if (!q.counter || !q.points || !q.normals || (!q.results && !q.rgba8) || q.ao_samples > 16u) return false;
+    // the live-lane count at or below which a wave visits its refill point (RT_POINTQ_REFILL; at most 63)
+    constexpr uint32_t thr = RT_POINTQ_REFILL < 63 ? RT_POINTQ_REFILL : 63;
+    const PointArgs pa{{q.eye[0], q.eye[1], q.eye[2]}, q.ao_samples, q.seed};
+    with_landscape(a, [&](auto l_tag) {
+        with_bool(q.steps != nullptr, [&](auto steps_tag) {
+            hipLaunchKernelGGL((k_shadepoints<decltype(l_tag)::value, decltype(steps_tag)::value>), dim3(q.blocks),
+                               dim3(1024), 0, a.stream, a.consts, a.perm2d, a.grad, q.points, q.normals, q.results,
+                               q.rgba8, q.steps, q.n, pa, q.counter, thr);
         });
     });
     return true;

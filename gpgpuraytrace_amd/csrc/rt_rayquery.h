@@ -1,10 +1,11 @@
 // rt_rayquery.h -- host-only decisions of rt_terrain_trace_rays, rt_terrain_trace_surface,
-// rt_terrain_shade_rays and the field queries rt_terrain_sample_field / rt_terrain_sample_lattice
-// (include/frosttrace.h): the option blocks' validation, the choice of the kernel shape, its lanes per ray,
-// its strips and its grid, the layout of the host forms' device block, and the scratch layout, grids and mask
-// arithmetic of rt_terrain_extract_mesh.  No HIP in here (the mask arithmetic is marked __host__ __device__ under
-// hipcc only, for k_meshcount): tests/tools/rayquery_check.cpp, surfquery_check.cpp, shadequery_check.cpp,
-// fieldquery_check.cpp, meshquery_check.cpp and querylayout_check.cpp drive it stand-alone under ASan + UBSan.
+// rt_terrain_shade_rays, rt_terrain_shade_points and the field queries rt_terrain_sample_field /
+// rt_terrain_sample_lattice (include/frosttrace.h): the option blocks' validation, the choice of the kernel shape,
+// its lanes per ray, its strips and its grid, the layout of the host forms' device block, and the scratch layout,
+// grids and mask arithmetic of rt_terrain_extract_mesh.  No HIP in here (the mask arithmetic is marked
+// __host__ __device__ under hipcc only, for k_meshcount): tests/tools/rayquery_check.cpp, surfquery_check.cpp,
+// shadequery_check.cpp, pointquery_check.cpp, fieldquery_check.cpp, meshquery_check.cpp and querylayout_check.cpp
+// drive it stand-alone under ASan + UBSan.
 #pragma once
 
 #include <cstddef>
@@ -211,6 +212,49 @@ inline int plan_shade(int n, uint32_t flags, uint32_t max_blocks, int cus, Plan*
     return plan(n, false, kForceLanes, max_blocks, cus, 0, 0, out, why);
 }
 
+// ---- point shading (rt_terrain_shade_points): its own option block, the lanes shape only ----
+
+// the first version of rt_point_options: size, flags, eye[3], max_blocks, ao_samples, seed
+constexpr uint32_t kPointOptSizeV1 = 32u;
+// ao_dir packs the AO ray's index into 4 bits
+constexpr uint32_t kPointMaxAO = 16u;
+
+struct PointOptions : Options {
+    uint32_t ao_samples = 0, seed = 0;
+};
+
+// `opt` is the caller's rt_point_options (may be null: the defaults), read as far as the first version reaches.
+inline int parse_point_options(const void* opt, PointOptions* out, const char** why)
+{
+    *out = PointOptions{};
+    if (!opt) return OK;
+    if (!parse_prefix(opt, kPointOptSizeV1, out)) {
+        *why = "rt_point_options.size is smaller than the struct's first version";
+        return INVALID;
+    }
+    if (out->flags & ~kEye) {
+        *why = "rt_point_options.flags has bits other than RT_RAYS_EYE";
+        return INVALID;
+    }
+    const char* p = static_cast<const char*>(opt);
+    std::memcpy(&out->ao_samples, p + 24, 4);
+    std::memcpy(&out->seed, p + 28, 4);
+    if (out->ao_samples > kPointMaxAO) {
+        *why = "rt_point_options.ao_samples is above 16";
+        return INVALID;
+    }
+    return OK;
+}
+
+// the plan of a point shading query of n >= 1 points: always lanes, its grid min(ceil(n / 1024), cus, max_blocks)
+inline Plan plan_points(int n, uint32_t max_blocks, int cus)
+{
+    Plan p;
+    const char* why = "";
+    plan(n, false, kForceLanes, max_blocks, cus, 0, 0, &p, &why);
+    return p;
+}
+
 // ---- field queries (rt_terrain_sample_field, rt_terrain_sample_lattice): density and normal at points ----
 
 // rt_field_options.flags beside kEye (RT_FIELD_NORMAL); every other bit is an error
@@ -315,10 +359,10 @@ inline FieldPlan plan_field_lattice(const uint32_t dims[3], bool nomadplains, ui
 
 // ---- the host forms' device block: one allocation holding a query's arrays ----
 
-// bytes per element of the arrays: a packed ray, a packed point, a ray result, a surface or shaded result, an
-// RGBA8 pixel, a ray's or surface ray's step count, a shaded ray's two
-constexpr size_t kRayBytes = 32, kPointBytes = 16, kRayResultBytes = 16, kSurfResultBytes = 32, kPixelBytes = 4,
-                 kStepsBytes = 4, kShadeStepsBytes = 8;
+// bytes per element of the arrays: a packed ray, a packed point (or normal), a ray result, a surface or shaded
+// result, a shaded point's result, an RGBA8 pixel, a ray's or surface ray's step count, a shaded ray's or point's two
+constexpr size_t kRayBytes = 32, kPointBytes = 16, kRayResultBytes = 16, kSurfResultBytes = 32, kPointResultBytes = 16,
+                 kPixelBytes = 4, kStepsBytes = 4, kShadeStepsBytes = 8;
 // a field result's bytes per point: the density, or with the normal {n.xyz, d}
 inline size_t field_stride(uint32_t flags) { return (flags & kFieldNormal) ? 16 : 4; }
 // a lattice's occupancy: one bit a point, ceil(nx / 32) words a row

@@ -3188,6 +3188,86 @@ extern "C" int rt_terrain_shade_rays(rt_compute c, const float* origins, const f
 }
 
 // ---------------------------------------------------------------------------
+// rt_terrain_shade_points: getColor with its shadow ray and the AO factor at caller-supplied points and normals
+// (include/frosttrace.h).  The query state (Shader::query, the claim counter) is the ray queries'; the eye is a
+// kernel argument and the constants' copy is the compute's as it is (no sky here).
+namespace {
+
+int shade_points_enqueue(rt_compute c, const void* points_device, const void* normals_device, uint32_t n,
+                         const rtq::PointOptions& o, void* results_device, void* rgba8_device, void* steps_device)
+{
+    rt_device dev = c->dev;
+    RtLaunch a;
+    RtPointQuery q{};
+    if (int rc = query_prepare(c, o, false, &a, q.eye)) return rc;
+    q.points = (const float4*)points_device;
+    q.normals = (const float4*)normals_device;
+    q.results = (float4*)results_device;
+    q.rgba8 = (uint32_t*)rgba8_device;
+    q.steps = (uint32_t*)steps_device;
+    q.n = n;
+    q.ao_samples = o.ao_samples;
+    q.seed = o.seed;
+    q.blocks = rtq::plan_points((int)n, o.max_blocks, cus_of(dev)).blocks;
+    if (int rc = arm_counter(dev, &q.counter)) return rc;
+    return query_launched(rt_launch_shadepoints(a, q), "rt_terrain_shade_points: no kernel for this query");
+}
+
+const QueryFamily<rtq::PointOptions> kPointFamily{"rt_terrain_shade_points", "point", rtq::parse_point_options};
+
+// point shading's clause
+auto points_clause(rt_compute c)
+{
+    return [=](const rtq::PointOptions&, uint32_t*) -> int {
+        if (c->shader->kind != KIND_TRACESCREEN)
+            return fail(RT_ERR_INVALID,
+                        "rt_terrain_shade_points: a camerarays compute has no SunDirection; pass the tracescreen compute");
+        return RT_OK;
+    };
+}
+
+} // namespace
+
+extern "C" int rt_terrain_shade_points_device(rt_compute c, const void* points_device, const void* normals_device, int n,
+                                              const rt_point_options* opt, void* results_device, void* rgba8_device,
+                                              void* steps_device)
+{
+    return query_entry(
+        c, kPointFamily, n, opt, points_clause(c),
+        !points_device || !normals_device  ? "rt_terrain_shade_points_device: null points or normals"
+        : !results_device && !rgba8_device ? "rt_terrain_shade_points_device: results and rgba8 are both null"
+                                           : nullptr,
+        [&](const rtq::PointOptions& o, uint32_t np) {
+            return shade_points_enqueue(c, points_device, normals_device, np, o, results_device, rgba8_device,
+                                        steps_device);
+        });
+}
+
+extern "C" int rt_terrain_shade_points(rt_compute c, const float* points, const float* normals, int n,
+                                       const rt_point_options* opt, float* results, uint32_t* rgba8, uint32_t* steps)
+{
+    return query_entry(
+        c, kPointFamily, n, opt, points_clause(c),
+        !points || !normals  ? "rt_terrain_shade_points: null points or normals"
+        : !results && !rgba8 ? "rt_terrain_shade_points: results and rgba8 are both null"
+                             : nullptr,
+        [&](const rtq::PointOptions& o, uint32_t np) {
+            std::vector<float> packed((size_t)np * 8);
+            rtq::pack_points(points, n, packed.data());
+            rtq::pack_points(normals, n, packed.data() + (size_t)np * 4);
+            // one device block: the packed points, the packed normals, the results, the pixels, the step counts
+            const HostPart parts[] = {{np * rtq::kPointBytes, packed.data(), nullptr},
+                                      {np * rtq::kPointBytes, packed.data() + (size_t)np * 4, nullptr},
+                                      {results ? np * rtq::kPointResultBytes : 0, nullptr, results},
+                                      {rgba8 ? np * rtq::kPixelBytes : 0, nullptr, rgba8},
+                                      {steps ? np * rtq::kShadeStepsBytes : 0, nullptr, steps}};
+            return host_form(c->dev, parts, [&](char* const* at) {
+                return shade_points_enqueue(c, at[0], at[1], np, o, at[2], at[3], at[4]);
+            });
+        });
+}
+
+// ---------------------------------------------------------------------------
 // rt_terrain_sample_field / rt_terrain_sample_lattice: the density field and its normal at points and on a lattice
 // (include/frosttrace.h).  The query state (Shader::query) is the ray queries'; the eye is a kernel argument.
 namespace {

@@ -118,6 +118,16 @@
 #define RT_SHADEQ_REFILL 32
 #endif
 
+// k_shadepoints (point shading): the same threshold for its refill point, where ended shadow and AO marches move on
+// to their point's next ray, finished points are stored and idle lanes claim points and take the colour's FBM.
+// The 154,469 vertices of the README's mesh at K = 4, ms per query (lane utilisation of the march steps), builds
+// with the counters: 8: 2.20 (39%), 16: 2.10 (42%), 24: 1.98 (45%), 32: 1.88 (47%), 40: 1.86 (48%), 48: 1.87 (49%),
+// 56: 1.91 (49%), spreads 1-4%; at K = 0 all lie within 2% (profiles/r15/shade_points.md).  32 to 56 are not told
+// apart, so RT_SHADEQ_REFILL's value, where this started, stays.
+#ifndef RT_POINTQ_REFILL
+#define RT_POINTQ_REFILL 32
+#endif
+
 // RT_SKY_EXIT: the product k_trace (nomadplains, not the STATS kernels) ends a primary ray whose direction
 // does not descend once its next sample lies above the terrain's ceiling kSkyCeil (rt_shader.h sky_exit;
 // DESIGN.md section 2, rule R10): the ray is a miss whatever the rest of its march does, and a fog-free miss
@@ -145,7 +155,7 @@
 // RT_WAVE_TRACE          per-wave timeline of k_trace (make trace; scripts/wave_trace.py); fields 23-27: segment-job
 //                        time / jobs / loop steps, lane-refill long-ray loop steps / time
 // RT_LIVE_HIST           histogram of live lanes per primary march step (rt_debug_live_hist)
-// RT_QUERY_UTIL          lane utilisation of the ray, surface and shaded queries' lane kernels' waves
+// RT_QUERY_UTIL          lane utilisation of the ray, surface, shaded and point queries' lane kernels' waves
 //                        (rt_debug_query_util; scripts/*_query_bench.py)
 // RT_COUNT_PRIMARY_STEPS count live lanes per primary march step as noise (scripts/phase_util.py)
 // RT_COUNT_LONG_STEPS=k  the same for long-ray steps (1 always, 2 after the drain, 3 before)

@@ -755,6 +755,49 @@ class Terrain:
                                                 results_ptr or None, rgba8_ptr or None, steps_ptr or None)
         return rc == _native.RT_OK
 
+    def shade_points(self, points, normals, eye=None, ao_samples=0, seed=0, rgba8=False, steps=False, max_blocks=0):
+        """rt_terrain_shade_points: what the terrain LOOKS like at n points the caller already holds -- getColor
+        with the sun's shadow ray, and the AO factor of ao_samples (0..16) hemisphere rays about the normal --
+        exactly as a frame computes both for a pixel whose primary ray ended there, without the view ray's fog and
+        sky blends.  points: (n, 3), or (n, 4) rows x y z _ (extract_mesh_device's vertices); normals: (n, 3), or
+        (n, 4) rows nx ny nz _ (sample_field(normals=True), extract_mesh's normals), used as given.  eye: the LOD
+        eye and the viewpoint of the colour (default: the camera's).  seed: any uint32; the AO directions are a
+        hash of (point index, seed, k).  The sun is the Terrain's (set_time_of_day).
+        Returns results (n, 4) float32 -- colour rgb (not saturated, not multiplied by ao), ao -- or a tuple
+        (results, [pixels (n,) uint32 RGBA8 of ao times the saturated colour, R in the low byte, alpha 255, if
+        rgba8], [steps (n, 2) uint32: shadow iterations and the AO rays' sum, if steps]); None if the call fails
+        (lib().rt_last_error()).  max_blocks caps the persistent grid.  Blocking; uses the tracescreen compute;
+        needs set_camera() first."""
+        p, nr = _xyz_rows(points), _xyz_rows(normals)
+        if len(p) != len(nr):
+            raise ValueError("shade_points: %d points, %d normals" % (len(p), len(nr)))
+        n = len(p)
+        opt = point_options(eye, ao_samples, seed, max_blocks)
+        self.update_shaders()
+        res = np.empty((n, 4), np.float32)
+        px = np.empty(n, np.uint32) if rgba8 else None
+        st = np.empty((n, 2), np.uint32) if steps else None
+        rc = lib().rt_terrain_shade_points(self.compute._h, p.ctypes.data, nr.ctypes.data, n, C.byref(opt),
+                                           res.ctypes.data, px.ctypes.data if rgba8 else None,
+                                           st.ctypes.data if steps else None)
+        if rc != _native.RT_OK:
+            return None
+        out = (res,) + ((px,) if rgba8 else ()) + ((st,) if steps else ())
+        return out if len(out) > 1 else res
+
+    def shade_points_device(self, points_ptr, normals_ptr, n, results_ptr=0, rgba8_ptr=0, steps_ptr=0, eye=None,
+                            ao_samples=0, seed=0, max_blocks=0):
+        """rt_terrain_shade_points_device: the same for device arrays -- points_ptr and normals_ptr n x 4 float32
+        (x y z _ and nx ny nz _, the spare words ignored: extract_mesh_device's vertices and normals as they are),
+        results_ptr n x 4 float32 or 0, rgba8_ptr n uint32 or 0 (one of the two at least), steps_ptr n x 2 uint32
+        or 0; points, normals and results 16-byte aligned -- enqueued on the device's stream with no host
+        synchronisation.  True on success."""
+        opt = point_options(eye, ao_samples, seed, max_blocks)
+        self.update_shaders()
+        rc = lib().rt_terrain_shade_points_device(self.compute._h, points_ptr or None, normals_ptr or None, int(n),
+                                                  C.byref(opt), results_ptr or None, rgba8_ptr or None,
+                                                  steps_ptr or None)
+        return rc == _native.RT_OK
 
     def sample_field(self, points, eye=None, normals=False, max_blocks=0):
         """rt_terrain_sample_field: what the terrain IS at n points -- the density getDensity gives (> 0 inside),
@@ -810,14 +853,27 @@ class Terrain:
                                                     results_ptr or None, occupancy_ptr or None)
         return rc == _native.RT_OK
 
-    def extract_mesh(self, origin, spacing, dims, eye=None, normals=True, max_blocks=0):
+    def extract_mesh(self, origin, spacing, dims, eye=None, normals=True, max_blocks=0, colors=False, ao_samples=0,
+                     seed=0):
         """rt_terrain_extract_mesh: the terrain's surface inside the lattice (sample_lattice's origin, spacing and
         dims) as a surface-nets triangle mesh, extracted on the device.  Returns (vertices (nv, 3) float32,
         normals (nv, 4) float32 rows getNormal xyz, density -- or None without normals --, triangles (nt, 3) uint32
         wound so that their normals point out of the terrain, cells (nv,) uint32: each vertex's cell index
         (cz (ny - 1) + cy) (nx - 1) + cx); None if a call fails.  Two calls: one that counts and one of the exact
         size, so the lattice's density is computed twice; keep the arrays on the device and size them yourself
-        (extract_mesh_device) where that matters.  Blocking; uses the camerarays compute."""
+        (extract_mesh_device) where that matters.  Blocking; uses the camerarays compute.
+        colors: one more array at the end, (nv,) uint32 RGBA8 -- shade_points' pixels for the vertices at their
+        normals with the same eye, ao_samples and seed (the tracescreen compute); it needs normals."""
+        if colors and not normals:
+            raise ValueError("extract_mesh: colors=True shades the vertices at their normals; it needs normals=True")
+        mesh = self._extract_mesh(origin, spacing, dims, eye, normals, max_blocks)
+        if mesh is None or not colors:
+            return mesh
+        shaded = self.shade_points(mesh[0], mesh[1], eye=eye, ao_samples=ao_samples, seed=seed, rgba8=True,
+                                   max_blocks=max_blocks)
+        return None if shaded is None else mesh + (shaded[1],)
+
+    def _extract_mesh(self, origin, spacing, dims, eye, normals, max_blocks):
         lat = lattice(origin, spacing, dims)
         opt = field_options(eye, False, max_blocks)
         self.update_shaders()
@@ -880,6 +936,29 @@ def lattice(origin, spacing, dims):
     lat.spacing[:] = [float(x) for x in np.asarray(spacing, np.float32).reshape(3)]
     lat.dims[:] = [int(x) for x in dims]
     return lat
+
+
+def _xyz_rows(a):
+    """(n, 3) float32, contiguous, of (n, 3) rows or of (n, 4) rows whose spare word is dropped."""
+    a = np.asarray(a, np.float32)
+    if a.ndim == 2 and a.shape[1] == 4:
+        a = a[:, :3]
+    return np.ascontiguousarray(a).reshape(-1, 3)
+
+
+def point_options(eye=None, ao_samples=0, seed=0, max_blocks=0):
+    """An rt_point_options block: the eye (None: the compute's Eye), the AO rays a point (0..16), the seed of
+    their directions' hash, the grid's cap."""
+    opt = _native.RtPointOptions()
+    opt.size = C.sizeof(_native.RtPointOptions)
+    opt.flags = 0
+    if eye is not None:
+        opt.flags |= _native.RT_RAYS_EYE
+        opt.eye[:] = [float(x) for x in np.asarray(eye, np.float32).reshape(3)]
+    opt.max_blocks = int(max_blocks)
+    opt.ao_samples = int(ao_samples)
+    opt.seed = int(seed) & 0xffffffff
+    return opt
 
 
 def pack_points(points):

@@ -77,16 +77,31 @@ def bgrx_to_rgb(bgrx):
     return b[..., 2::-1].copy()
 
 
-def write_obj(path, vertices, triangles, normals=None):
+def write_obj(path, vertices, triangles, normals=None, colors=None):
     """A triangle mesh (Terrain.extract_mesh) -> Wavefront OBJ: `v x y z` lines, with normals (nv, 3 or 4: the
     first three columns) `vn x y z` lines, and faces `f a b c` (or `f a//a b//b c//c`) with 1-based indices.
-    Floats are written with 9 significant digits, which reads back to the same float32."""
+    Floats are written with 9 significant digits, which reads back to the same float32.
+    colors: vertex colours as the common `v x y z r g b` extension, channels in 0..1 -- (nv,) RGBA8 words (R in
+    the low byte: extract_mesh(colors=True), shade_points(rgba8=True); a channel is byte / 255) or (nv, 3) floats
+    written as they are.  Without colors the file is what it always was."""
     v = np.asarray(vertices, np.float32).reshape(-1, 3)
     t = np.asarray(triangles, np.int64).reshape(-1, 3) + 1
     n = None if normals is None else np.asarray(normals, np.float32).reshape(len(v), -1)[:, :3]
+    if colors is not None:
+        c = np.asarray(colors)
+        if c.ndim == 1 and c.dtype.kind in "ui":
+            w = c.astype(np.uint32)
+            c = np.stack([w & 255, (w >> 8) & 255, (w >> 16) & 255], axis=1).astype(np.float32) / np.float32(255)
+        c = np.asarray(c, np.float32)
+        if c.shape != (len(v), 3):
+            raise ValueError("write_obj: colors must be (nv,) RGBA8 words or (nv, 3) floats for %d vertices" % len(v))
+        v = np.concatenate([v, c], axis=1)
     with open(path, "w") as f:
         f.write("# %d vertices, %d triangles\n" % (len(v), len(t)))
-        f.writelines("v %.9g %.9g %.9g\n" % tuple(map(float, p)) for p in v)
+        if colors is not None:
+            f.writelines("v %.9g %.9g %.9g %.9g %.9g %.9g\n" % tuple(map(float, p)) for p in v)
+        else:
+            f.writelines("v %.9g %.9g %.9g\n" % tuple(map(float, p)) for p in v)
         if n is not None:
             f.writelines("vn %.9g %.9g %.9g\n" % tuple(map(float, p)) for p in n)
             f.writelines("f %d//%d %d//%d %d//%d\n" % (a, a, b, b, c, c) for a, b, c in t)

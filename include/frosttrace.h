@@ -526,7 +526,8 @@ int rt_terrain_trace_surface_device(rt_compute cs, const void* rays_device, int 
  *   SunDirection, RECORDING and the landscape constants come from the compute, which must be a TRACESCREEN
  *         compute (camerarays has no SunDirection).  Its AA_SAMPLES, RT_MAX_STEPS and RT_AO_SAMPLES macros are
  *         ignored: one sample per ray, the option block's max_steps is the cap.
- *   NO ambient occlusion: the result is the sample before any AO factor, whatever the compute was built with.
+ *   NO ambient occlusion: the result is the sample before any AO factor, whatever the compute was built with
+ *         (rt_terrain_shade_points gives the AO factor at a point, e.g. at result_i's pd.xyz).
  *         Nor a segment shape or a sun per ray; the option block's size field leaves room for them later.
  *   A zero dir or non-finite inputs give unspecified results; the kernel still ends.
  * The option block is rt_surface_options, parsed as for the surface queries: RT_RAYS_EYE, RT_SURFACE_PARAMS
@@ -547,6 +548,69 @@ int rt_terrain_shade_rays(rt_compute screen_cs, const float* origins, const floa
                           const rt_surface_options* opt, float* results, uint32_t* rgba8, uint32_t* steps);
 int rt_terrain_shade_rays_device(rt_compute screen_cs, const void* rays_device, int n, const rt_surface_options* opt,
                                  void* results_device, void* rgba8_device, void* steps_device);
+
+/* ---- point shading (ABI 9, additive; no reference counterpart) ----
+ * What the terrain LOOKS like at a point the host already holds, without a view ray: its colour with the sun's
+ * shadow, and how occluded it is.  Vertex colours and AO for an extracted mesh (rt_terrain_extract_mesh's vertices
+ * and normals arrays are read as they are), light and AO probes, the tint of a decal or an object at an
+ * rt_terrain_trace_surface hit, per-vertex AO for any mesh laid on the terrain.  For point i with position p_i and
+ * normal n_i, one eye E per call and K = ao_samples, the result is what a frame computes for a pixel whose primary
+ * ray ended at p_i, before the view ray's fog and sky blends:
+ *     dist   = length(p_i - E);  pdn = (p_i - E) * rcp(dist)                            (normalize(p_i - E))
+ *     color  = getColor(p_i, n_i, pdn, dist)            (color.hlsl of the landscape; its shadow ray: traceRay(p_i,
+ *                                               0.4, 100, precision(dist), SunDirection, fog ON, skiprefine ON))
+ *     K > 0 : for k = 0..K-1:  rr_k = traceRay(p_i, 0.4, 25, precision(dist), ao_dir(n_i, px = i, py = seed, a = 0, k),
+ *                                              fog OFF, skiprefine ON);  occ += rr_k.density > 0
+ *             ao = fma(-0.6, occ * rcp(K), 1)                          (the AO extension of the frames, unchanged)
+ *     K == 0: ao = 1
+ *     result_i = float4(color.rgb, ao)                 color NOT saturated and NOT multiplied by ao
+ *     rgba8_i  = unorm8(saturate(color.rgb) * ao), alpha 255        a frame's rule: ao multiplies the saturated colour
+ *     steps_i  = { shadow iterations, sum of the K AO rays' iterations }
+ *   E     replaces Eye in the density's level of detail, as in every query, and is the viewpoint dist and pdn come
+ *         from: the specular term, simple's colour detail, and the shadow and AO rays' precision.  Without
+ *         RT_RAYS_EYE it is the compute's current Eye variable.  One per call.  p_i == E gives unspecified results;
+ *         the kernel still ends.
+ *   n_i   is used as given (a frame passes getNormal's unit normal).  A zero or non-finite normal, or a non-finite
+ *         point, gives unspecified results; the kernel still ends.
+ *   The AO directions are a hash of (i, seed, k): the same call gives the same bits, and another seed decorrelates
+ *         two bakes.  i is the point's index in the call.
+ *   SunDirection, RECORDING and the landscape constants come from the compute, which must be a TRACESCREEN compute
+ *         (camerarays has no SunDirection).  Its RT_AO_SAMPLES, AA_SAMPLES and RT_MAX_STEPS macros are ignored.
+ * Layouts: points are n x 4 floats x y z _ and normals n x 4 floats nx ny nz _, the spare words ignored: the field
+ *   queries' packed points and RT_FIELD_NORMAL results, and rt_terrain_extract_mesh's vertices (spare word: the cell
+ *   index) and normals (spare word: the density).  results n x 4 floats; rgba8 n uint32 (R in the low byte); steps
+ *   2n uint32.
+ * rt_point_options (opt may be NULL: all defaults, K = 0 and seed 0): size = sizeof(rt_point_options) of the
+ *   caller's header (later versions append fields; the first version is 32 bytes); flags: RT_RAYS_EYE, every other
+ *   bit is an error; max_blocks caps the persistent grid (0: every CU less rt_device_reserve_cus); ao_samples 0..16
+ *   (ao_dir packs k into 4 bits); seed any uint32.
+ * rt_terrain_shade_points: host arrays (points, normals: 3n floats each; results: 4n floats or NULL; rgba8: n
+ *   uint32 or NULL; steps: 2n uint32 or NULL); blocking.
+ * rt_terrain_shade_points_device: device arrays (points, normals and results 16-byte aligned; results, rgba8 and
+ *   steps may be NULL), enqueued on the compute's device stream with no host synchronisation: order other streams
+ *   with rt_device_wait_event / rt_device_record_event.
+ * Both: at least one of results and rgba8.  n == 0 is RT_OK and launches nothing.  RT_ERR_INVALID: n < 0,
+ *   n > 2^26, a NULL compute, points or normals, results and rgba8 both NULL, opt->size below 32, unknown flags,
+ *   ao_samples above 16, a camerarays compute.  RT_ERR_STATE without texPerm2D bound, or with the fail-safe word
+ *   set.  A query reads no frame state and changes none: it flushes no deferred frame, invalidates no ahead / fused
+ *   prepass or captured graph, and uploads the constants it needs to a copy of its own, so it may run between any
+ *   two renders.
+ * Out of scope: the view ray's fog and sky blends (rt_terrain_shade_rays has them); a sun or an eye per point;
+ *   getNormal inside the call (pass rt_terrain_sample_field's RT_FIELD_NORMAL results or the mesh's normals); a
+ *   caller-chosen AO range or strength. */
+typedef struct {
+    uint32_t size;
+    uint32_t flags;
+    float eye[3];
+    uint32_t max_blocks;
+    uint32_t ao_samples;
+    uint32_t seed;
+} rt_point_options;
+int rt_terrain_shade_points(rt_compute screen_cs, const float* points, const float* normals, int n,
+                            const rt_point_options* opt, float* results, uint32_t* rgba8, uint32_t* steps);
+int rt_terrain_shade_points_device(rt_compute screen_cs, const void* points_device, const void* normals_device, int n,
+                                   const rt_point_options* opt, void* results_device, void* rgba8_device,
+                                   void* steps_device);
 
 /* ---- field queries (ABI 9, additive; no reference counterpart) ----
  * What the terrain IS at a place, without a ray: the density field itself (getDensity, > 0 inside) and its normal.
