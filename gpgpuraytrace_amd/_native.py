@@ -75,6 +75,14 @@ class RtLattice(C.Structure):
     _fields_ = [("origin", C.c_float * 3), ("spacing", C.c_float * 3), ("dims", C.c_uint32 * 3)]
 
 
+RT_DIST_FAR = 0xFFFFFFFF  # a d2 without a point of the other state (or beyond max_cells)
+
+
+class RtDistanceOptions(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("eye", C.c_float * 3), ("max_blocks", C.c_uint32),
+                ("max_cells", C.c_uint32)]
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -173,6 +181,12 @@ SIGNATURES = {
                                      C.c_uint32, _vp]),
     "rt_terrain_extract_mesh_device": (_i, [_vp, C.POINTER(RtLattice), C.POINTER(RtFieldOptions), _vp, _sz, _vp, _vp,
                                             C.c_uint32, _vp, C.c_uint32, _vp]),
+    # distance fields: exact squared lattice distance (uint32) and signed distance (float32) of a lattice's points to
+    # the other occupancy state; occupancy words in (or null: the terrain's); the device form takes its scratch block
+    "rt_terrain_distance_scratch_bytes": (_sz, [C.POINTER(RtLattice)]),
+    "rt_terrain_distance_field": (_i, [_vp, C.POINTER(RtLattice), C.POINTER(RtDistanceOptions), _vp, _vp, _vp]),
+    "rt_terrain_distance_field_device": (_i, [_vp, C.POINTER(RtLattice), C.POINTER(RtDistanceOptions), _vp, _vp, _sz,
+                                              _vp, _vp]),
     "rt_noise_generate": (_i, [C.c_uint32, _i, _vp, _vp]),
     "rt_terrain_set_target_depths": (_i, [_vp, _vp]),
     "rt_recorder_create": (_i, [_vp, _i, _i, _cp, C.POINTER(_vp)]),

@@ -246,6 +246,26 @@ struct RtMeshQuery {
 };
 bool rt_launch_meshquery(const RtLaunch& a, const RtMeshQuery& q);
 
+// A distance field's three passes (rt_terrain_distance_field; the definition is in include/frosttrace.h, the
+// scratch layout and the row arithmetic in rt_rayquery.h): `occupancy` holds the lattice's words in
+// rt_terrain_sample_lattice's layout, the padding bits anything (the caller's, or a lattice RtFieldQuery's on the
+// same stream).  k_distrows fills `rows` (a word a point), k_distcolumns the two planes of `planes` (points uint32
+// each: inside set, outside set), k_distfinish stores d2 and / or distance (either may be null, not both).
+// reach / limit2: rtq::distance_bound; abs_spacing: |spacing[0]|, read with `distance` only.  All dims >= 1 with
+// a product of 2^26 at most; blocks of rtq::kDistThreads threads.  false: nothing launched.
+struct RtDistanceQuery {
+    const uint32_t* occupancy;
+    uint32_t* rows;
+    uint32_t* planes;
+    uint32_t dims[3];
+    uint32_t reach, limit2;
+    float abs_spacing;
+    uint32_t* d2;
+    float* distance;
+    uint32_t blocks;
+};
+bool rt_launch_distancequery(const RtLaunch& a, const RtDistanceQuery& q);
+
 #define RT_TILE 32
 #define RT_FIN_SLOTS 1536 // k_trace's fin pool slots per block
 #define RT_AO_POOL_SLOTS 256 // k_trace's AO counter slots per block (LDS) and their colours (cpool)

@@ -3330,6 +3330,113 @@ bool rt_launch_meshquery(const RtLaunch& a, const RtMeshQuery& q)
 }
 
 // ---------------------------------------------------------------------------
+// Distance fields (rt_terrain_distance_field): the exact squared lattice distance of every point to the nearest
+// point of the other state, from the occupancy words alone (include/frosttrace.h has the definition, rt_rayquery.h
+// the scratch layout and the row arithmetic).  A separable transform to both sets, inside and outside, in three
+// passes on one stream.  Every pass takes a thread a point in result order, so consecutive lanes are consecutive
+// ix (a wave may run over a row's end into the next row) and every load and store of a wave is a run of
+// consecutive words.  The y and z passes scan outward from the point, o = 1, 2, ..., and stop once o * o can no
+// longer improve on the best found (or o passes max_cells): exact, with no per-thread stack and no LDS.  Every
+// loop is bounded by a dim.
+namespace {
+
+struct DistGrid {
+    uint32_t nx, ny, nz, points;
+    uint32_t reach, limit2; // rtq::distance_bound
+};
+
+// the x pass: the row distances to both sets (rtq::dist_row_pack), 16 bits each.  The lanes of one occupancy word
+// walk the row's words together, so those loads are the same address in 32 lanes.
+__global__ void __launch_bounds__(rtq::kDistThreads) k_distrows(const uint32_t* __restrict__ occ, uint32_t* __restrict__ rows,
+                                                               DistGrid g)
+{
+    const uint32_t words = (g.nx + 31u) / 32u;
+    for (uint32_t i = blockIdx.x * rtq::kDistThreads + threadIdx.x; i < g.points; i += gridDim.x * rtq::kDistThreads) {
+        const uint32_t row = i / g.nx, ix = i - row * g.nx;
+        const rtq::DistRowWord r = rtq::dist_row_word(occ + (size_t)row * words, g.nx, ix >> 5);
+        rows[i] = rtq::dist_row_pack(r, ix & 31u);
+    }
+}
+
+// one neighbour of the y pass at offset o (oo = o * o): its row distances folded into both bests
+__device__ __forceinline__ void dist_fold_row(uint32_t w, uint32_t oo, uint32_t& best_in, uint32_t& best_out)
+{
+    const uint32_t a = w & 0xffffu, b = w >> 16;
+    if (a != rtq::kDistRowFar) best_in = min(best_in, a * a + oo);
+    if (b != rtq::kDistRowFar) best_out = min(best_out, b * b + oo);
+}
+
+// the y pass: h(iy) = min over k of g(k)^2 + (iy - k)^2 down the column (ix, iz), for both sets, into the two planes
+__global__ void __launch_bounds__(rtq::kDistThreads) k_distcolumns(const uint32_t* __restrict__ rows, uint32_t* __restrict__ planes,
+                                                                  DistGrid g)
+{
+    for (uint32_t i = blockIdx.x * rtq::kDistThreads + threadIdx.x; i < g.points; i += gridDim.x * rtq::kDistThreads) {
+        const uint32_t iy = (i / g.nx) % g.ny, up = iy, down = g.ny - 1u - iy;
+        uint32_t best_in = rtq::kDistFar, best_out = rtq::kDistFar;
+        dist_fold_row(rows[i], 0u, best_in, best_out);
+        const uint32_t span = up > down ? up : down, last = span < g.reach ? span : g.reach;
+        for (uint32_t o = 1u; o <= last; ++o) {
+            const uint32_t oo = o * o;
+            if (oo >= best_in && oo >= best_out) break;
+            if (o <= up) dist_fold_row(rows[i - o * g.nx], oo, best_in, best_out);
+            if (o <= down) dist_fold_row(rows[i + o * g.nx], oo, best_in, best_out);
+        }
+        planes[i] = best_in;
+        planes[(size_t)g.points + i] = best_out;
+    }
+}
+
+// the z pass: the same down the column (ix, iy) over the plane of the set the point is not in, then max_cells and
+// the stores.  RT_DIST_FAR is never added to.
+__global__ void __launch_bounds__(rtq::kDistThreads) k_distfinish(const uint32_t* __restrict__ occ, const uint32_t* __restrict__ planes,
+                                                                 uint32_t* __restrict__ d2_out, float* __restrict__ dist_out,
+                                                                 float abs_spacing, DistGrid g)
+{
+    const uint32_t words = (g.nx + 31u) / 32u, plane = g.nx * g.ny;
+    for (uint32_t i = blockIdx.x * rtq::kDistThreads + threadIdx.x; i < g.points; i += gridDim.x * rtq::kDistThreads) {
+        const uint32_t row = i / g.nx, ix = i - row * g.nx, iz = row / g.ny, up = iz, down = g.nz - 1u - iz;
+        const bool inside = (occ[(size_t)row * words + (ix >> 5)] >> (ix & 31u)) & 1u;
+        const uint32_t* __restrict__ h = planes + (inside ? (size_t)g.points : 0); // an inside point: the outside set
+        uint32_t best = h[i];
+        const uint32_t span = up > down ? up : down, last = span < g.reach ? span : g.reach;
+        for (uint32_t o = 1u; o <= last; ++o) {
+            const uint32_t oo = o * o;
+            if (oo >= best) break;
+            if (o <= up) {
+                const uint32_t v = h[i - o * plane];
+                if (v != rtq::kDistFar) best = min(best, v + oo);
+            }
+            if (o <= down) {
+                const uint32_t v = h[i + o * plane];
+                if (v != rtq::kDistFar) best = min(best, v + oo);
+            }
+        }
+        const uint32_t d2 = best > g.limit2 ? rtq::kDistFar : best;
+        if (d2_out) d2_out[i] = d2;
+        if (dist_out) {
+            const float d = d2 == rtq::kDistFar ? __builtin_inff() : rtm::sqrt((float)d2) * abs_spacing;
+            dist_out[i] = inside ? -d : d;
+        }
+    }
+}
+
+} // namespace
+
+bool rt_launch_distancequery(const RtLaunch& a, const RtDistanceQuery& q)
+{
+    const uint64_t points = (uint64_t)q.dims[0] * q.dims[1] * q.dims[2];
+    if (points == 0 || points > (1u << 26) || q.blocks == 0) return false;
+    if (q.dims[0] > rtq::kMaxLatticeDim || q.dims[1] > rtq::kMaxLatticeDim || q.dims[2] > rtq::kMaxLatticeDim) return false;
+    if (!q.occupancy || !q.rows || !q.planes || (!q.d2 && !q.distance)) return false;
+    const DistGrid g{q.dims[0], q.dims[1], q.dims[2], (uint32_t)points, q.reach, q.limit2};
+    const dim3 grid(q.blocks), block(rtq::kDistThreads);
+    hipLaunchKernelGGL(k_distrows, grid, block, 0, a.stream, q.occupancy, q.rows, g);
+    hipLaunchKernelGGL(k_distcolumns, grid, block, 0, a.stream, q.rows, q.planes, g);
+    hipLaunchKernelGGL(k_distfinish, grid, block, 0, a.stream, q.occupancy, q.planes, q.d2, q.distance, q.abs_spacing, g);
+    return true;
+}
+
+// ---------------------------------------------------------------------------
 // Diagnostics: device evaluation of the numeric primitives, noise3d and
 // getDensity for the primitive-level parity tests (tests/test_gpu_parity.py).
 namespace {

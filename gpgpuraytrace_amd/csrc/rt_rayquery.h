@@ -529,4 +529,175 @@ inline MeshPlan plan_mesh(const MeshScratch& s, uint32_t max_vertices, uint32_t 
     return p;
 }
 
+// ---- distance fields (rt_terrain_distance_field): exact squared lattice distance to the other state ----
+//
+// A separable transform to both sets, the inside points and the outside points.  The x pass (k_distrows) works on
+// the occupancy words alone: for every point the distance along its row to the nearest inside point and to the
+// nearest outside point, 16 bits each in one word (kDistRowFar: the row has none).  The y pass (k_distcolumns) turns
+// those into the squared distance within the point's (x, y) plane, a uint32 per set (RT_DIST_FAR: none), and the z
+// pass (k_distfinish) into the squared distance to the set the point itself is not in.
+
+constexpr uint32_t kDistFar = 0xffffffffu; // RT_DIST_FAR
+constexpr uint32_t kDistRowFar = 0xffffu;  // a row distance is 4095 at most
+// the first version of rt_distance_options: size, flags, eye[3], max_blocks, max_cells
+constexpr uint32_t kDistOptSizeV1 = 28u;
+// a finite d2 is 3 * 4095^2 at most, below 7093^2: a max_cells from here on bounds nothing
+constexpr uint32_t kDistMaxCells = 7093u;
+
+struct DistanceOptions : Options {
+    uint32_t max_cells = 0; // 0: unbounded
+};
+
+// `opt` is the caller's rt_distance_options (may be null: the defaults), read as far as the first version reaches.
+inline int parse_distance_options(const void* opt, DistanceOptions* out, const char** why)
+{
+    *out = DistanceOptions{};
+    if (!opt) return OK;
+    if (!parse_prefix(opt, kDistOptSizeV1, out)) {
+        *why = "rt_distance_options.size is smaller than the struct's first version";
+        return INVALID;
+    }
+    if (out->flags & ~kEye) {
+        *why = "rt_distance_options.flags has bits other than RT_RAYS_EYE";
+        return INVALID;
+    }
+    std::memcpy(&out->max_cells, static_cast<const char*>(opt) + 24, 4);
+    return OK;
+}
+
+// what max_cells means to the kernels: `reach`, the largest offset a column scan has to look at (the dims bound it
+// anyway), and `limit2`, the largest d2 that stays finite
+struct DistanceBound {
+    uint32_t reach = kMaxLatticeDim, limit2 = kDistFar - 1u;
+};
+inline DistanceBound distance_bound(uint32_t max_cells)
+{
+    DistanceBound b;
+    if (max_cells && max_cells < kDistMaxCells) {
+        b.reach = max_cells;
+        b.limit2 = max_cells * max_cells;
+    }
+    return b;
+}
+
+// distance is defined on an isotropic lattice only: |sx| == |sy| == |sz| != 0 (a lattice check_lattice passed)
+inline bool distance_isotropic(const float spacing[3])
+{
+    const float a = spacing[0] < 0.0f ? -spacing[0] : spacing[0], b = spacing[1] < 0.0f ? -spacing[1] : spacing[1],
+                c = spacing[2] < 0.0f ? -spacing[2] : spacing[2];
+    return a != 0.0f && a == b && a == c;
+}
+
+// The part of an occupancy row that one of its words, w, needs: the word's inside and outside points (the padding
+// bits beyond nx cleared in both) and, per set, the distance from the word's first point, 32 w, back to the set's
+// nearest point in an earlier word and from the word's bit 31, point 32 w + 31, on to its nearest point in a later
+// word (kDistRowFar: none).
+struct DistRowWord {
+    uint32_t bits[2];          // [0] inside points, [1] outside points
+    uint32_t left[2], right[2];
+};
+
+RTQ_HD inline uint32_t dist_clz(uint32_t m) { return (uint32_t)__builtin_clz(m); } // m != 0
+RTQ_HD inline uint32_t dist_ctz(uint32_t m) { return (uint32_t)__builtin_ctz(m); } // m != 0
+
+// the points of word w of a row of nx points (32 w < nx) that exist
+RTQ_HD inline uint32_t dist_valid_bits(uint32_t nx, uint32_t w)
+{
+    const uint32_t left = nx - 32u * w;
+    return left >= 32u ? 0xffffffffu : (1u << left) - 1u;
+}
+
+// row: the ceil(nx / 32) occupancy words of one point row, whatever their padding bits hold; 32 w < nx.  Both word
+// loops are bounded by the row's words.
+RTQ_HD inline DistRowWord dist_row_word(const uint32_t* row, uint32_t nx, uint32_t w)
+{
+    const uint32_t words = (nx + 31u) / 32u;
+    DistRowWord r;
+    for (uint32_t set = 0; set < 2u; ++set) {
+        const uint32_t flip = set ? 0xffffffffu : 0u;
+        r.bits[set] = (row[w] ^ flip) & dist_valid_bits(nx, w);
+        r.left[set] = r.right[set] = kDistRowFar;
+        for (uint32_t v = w; v-- > 0u;) {
+            const uint32_t m = row[v] ^ flip; // (an earlier word has no padding)
+            if (m) {
+                r.left[set] = 32u * (w - v) - 31u + dist_clz(m);
+                break;
+            }
+        }
+        for (uint32_t v = w + 1u; v < words; ++v) {
+            const uint32_t m = (row[v] ^ flip) & dist_valid_bits(nx, v);
+            if (m) {
+                r.right[set] = 32u * (v - w) - 31u + dist_ctz(m);
+                break;
+            }
+        }
+    }
+    return r;
+}
+
+// the distance of the word's point b (32 w + b < nx) to the nearest point of `set` in its row, or kDistRowFar
+RTQ_HD inline uint32_t dist_row_point(const DistRowWord& r, uint32_t set, uint32_t b)
+{
+    const uint32_t below = r.bits[set] & (0xffffffffu >> (31u - b)), above = r.bits[set] & (0xffffffffu << b);
+    uint32_t dl = kDistRowFar, dr = kDistRowFar;
+    if (below) dl = b - (31u - dist_clz(below));
+    else if (r.left[set] != kDistRowFar) dl = r.left[set] + b;
+    if (above) dr = dist_ctz(above) - b;
+    else if (r.right[set] != kDistRowFar) dr = r.right[set] + (31u - b);
+    return dl < dr ? dl : dr;
+}
+
+// what k_distrows stores for a point: the distance to the nearest inside point in the low half, to the nearest
+// outside point in the high half
+RTQ_HD inline uint32_t dist_row_pack(const DistRowWord& r, uint32_t b)
+{
+    return dist_row_point(r, 0u, b) | (dist_row_point(r, 1u, b) << 16);
+}
+
+// The row arithmetic of the x pass for one word: in[b] / out[b] for every point 32 w + b < nx (the other entries
+// are left alone).
+inline void dist_row(const uint32_t* row, uint32_t nx, uint32_t w, uint16_t in[32], uint16_t out[32])
+{
+    const DistRowWord r = dist_row_word(row, nx, w);
+    for (uint32_t b = 0; b < 32u && 32u * w + b < nx; ++b) {
+        const uint32_t p = dist_row_pack(r, b);
+        in[b] = (uint16_t)(p & 0xffffu);
+        out[b] = (uint16_t)(p >> 16);
+    }
+}
+
+// The scratch block of a distance field, laid out by block_layout: the lattice's occupancy words (used when the
+// terrain's own occupancy is asked for), the x pass's word per point, and the y pass's two uint32 planes (inside
+// set, outside set).
+struct DistanceScratch {
+    uint32_t points = 0; // nx ny nz
+    BlockLayout lay;     // parts: occupancy, rows, planes; total 0 without points
+};
+enum { DIST_OCCUPANCY = 0, DIST_ROWS = 1, DIST_PLANES = 2 };
+
+// dims of a lattice that check_lattice passed
+inline DistanceScratch distance_scratch(const uint32_t dims[3])
+{
+    DistanceScratch s;
+    s.points = dims[0] * dims[1] * dims[2];
+    if (s.points == 0) return s;
+    const size_t bytes[3] = {occupancy_bytes(dims), (size_t)s.points * 4, (size_t)s.points * 8};
+    s.lay = block_layout(bytes, 3);
+    return s;
+}
+
+// The grid of the three passes: a thread a point in blocks of kDistThreads threads, a block striding over tiles of
+// kDistThreads consecutive points.  Light kernels without LDS, eight blocks a CU resident, so the grid is capped at
+// 8 blocks a CU (or at max_blocks).
+constexpr uint32_t kDistThreads = 256u;
+struct DistancePlan {
+    uint32_t blocks = 0;
+};
+inline DistancePlan plan_distance(uint32_t points, uint32_t max_blocks, int cus)
+{
+    DistancePlan p;
+    p.blocks = field_grid((points + kDistThreads - 1u) / kDistThreads, max_blocks, 8 * (cus > 0 ? cus : 1));
+    return p;
+}
+
 } // namespace rtq

@@ -2738,7 +2738,8 @@ extern "C" int rt_debug_math(rt_device d, int op, const float* a, const float* b
         HIP_TRY(hipMalloc(&da, 4));
         HIP_TRY(hipMalloc(&dy, 12));
         HIP_TRY(hipMemcpy(da, a, 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemset(dy, 0, 12));
+        // on the kernel's own stream: it does not wait for the null stream, where a memset may still be under way
+        HIP_TRY(hipMemsetAsync(dy, 0, 12, d->stream));
         rt_launch_debug_math(d->stream, op, da, da, dy, n);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(d->stream));
@@ -3526,6 +3527,104 @@ extern "C" int rt_terrain_extract_mesh_device(rt_compute c, const rt_lattice* la
 {
     return extract_mesh_entry("rt_terrain_extract_mesh_device", c, lat, opt, scratch_device, scratch_bytes, vertices_device,
                               normals_device, max_vertices, triangles_device, max_triangles, counts_device, false);
+}
+
+// ---------------------------------------------------------------------------
+// rt_terrain_distance_field: the exact squared lattice distance to the nearest point of the other state, and the
+// signed distance (include/frosttrace.h): the caller's occupancy words, or the lattice query's occupancy pass into
+// the scratch block, then the three distance passes (rt_launch_distancequery), all on the device stream.
+namespace {
+
+// enqueue one distance field (no host synchronisation, no allocation); the scratch block holds s.lay.total bytes;
+// occupancy null: the terrain's own
+int distance_field_enqueue(rt_compute c, const rtq::Lattice& l, const rtq::DistanceScratch& s,
+                           const rtq::DistanceOptions& o, const void* occupancy, char* scratch, void* d2, void* distance)
+{
+    rt_device dev = c->dev;
+    if (!occupancy) {
+        rtq::FieldOptions occ_opt = o; // the eye and the grid's cap
+        void* own = scratch + s.lay.offset[rtq::DIST_OCCUPANCY];
+        if (int rc = sample_field_enqueue(c, nullptr, &l, s.points, occ_opt, nullptr, own)) return rc;
+        occupancy = own;
+    }
+    const RtLaunch a = make_launch(dev, c->shader);
+    RtDistanceQuery q{};
+    q.occupancy = (const uint32_t*)occupancy;
+    q.rows = (uint32_t*)(scratch + s.lay.offset[rtq::DIST_ROWS]);
+    q.planes = (uint32_t*)(scratch + s.lay.offset[rtq::DIST_PLANES]);
+    memcpy(q.dims, l.dims, sizeof(q.dims));
+    const rtq::DistanceBound b = rtq::distance_bound(o.max_cells);
+    q.reach = b.reach;
+    q.limit2 = b.limit2;
+    q.abs_spacing = fabsf(l.spacing[0]);
+    q.d2 = (uint32_t*)d2;
+    q.distance = (float*)distance;
+    q.blocks = rtq::plan_distance(s.points, o.max_blocks, cus_of(dev)).blocks;
+    return query_launched(rt_launch_distancequery(a, q), "rt_terrain_distance_field: no kernel for this query");
+}
+
+// both entry points; host: the blocking form, whose arrays are the host's
+int distance_field_entry(const char* who, rt_compute c, const rt_lattice* lat, const rt_distance_options* opt,
+                         const void* occupancy, void* scratch, size_t scratch_bytes, void* d2, void* distance, bool host)
+{
+    const QueryFamily<rtq::DistanceOptions> f{who, nullptr, rtq::parse_distance_options};
+    rtq::Lattice l;
+    rtq::DistanceScratch s;
+    std::string both_null = std::string(who) + ": d2 and distance are both null";
+    return query_entry(
+        c, f, 0, opt,
+        [&](const rtq::DistanceOptions&, uint32_t* n) -> int {
+            const char* why = "";
+            if (int rc = rtq::check_lattice(lat, &l, n, &why)) return fail(rc, "%s: %s", who, why);
+            s = rtq::distance_scratch(l.dims);
+            if (distance && !rtq::distance_isotropic(l.spacing))
+                return fail(RT_ERR_INVALID, "%s: distance needs an isotropic lattice, |spacing| equal on the three axes and not 0",
+                            who);
+            if (!host && *n) {
+                if (!scratch || scratch_bytes < s.lay.total)
+                    return fail(RT_ERR_INVALID, "%s: the scratch block is null or below rt_terrain_distance_scratch_bytes", who);
+                if (((uintptr_t)scratch | (uintptr_t)occupancy | (uintptr_t)d2 | (uintptr_t)distance) % 4)
+                    return fail(RT_ERR_INVALID, "%s: the device arrays must be 4-byte aligned", who);
+            }
+            return RT_OK;
+        },
+        !d2 && !distance ? both_null.c_str() : nullptr,
+        [&](const rtq::DistanceOptions& o, uint32_t n) {
+            if (!host) return distance_field_enqueue(c, l, s, o, occupancy, (char*)scratch, d2, distance);
+            // one device block: the scratch, the caller's occupancy words, the two results
+            const HostPart parts[] = {{s.lay.total, nullptr, nullptr},
+                                      {occupancy ? rtq::occupancy_bytes(l.dims) : 0, occupancy, nullptr},
+                                      {d2 ? (size_t)n * 4 : 0, nullptr, d2},
+                                      {distance ? (size_t)n * 4 : 0, nullptr, distance}};
+            return host_form(c->dev, parts, [&](char* const* at) {
+                return distance_field_enqueue(c, l, s, o, at[1], at[0], at[2], at[3]);
+            });
+        });
+}
+
+} // namespace
+
+extern "C" size_t rt_terrain_distance_scratch_bytes(const rt_lattice* lat)
+{
+    rtq::Lattice l;
+    uint32_t n = 0;
+    const char* why = "";
+    if (rtq::check_lattice(lat, &l, &n, &why)) return 0;
+    return rtq::distance_scratch(l.dims).lay.total;
+}
+
+extern "C" int rt_terrain_distance_field(rt_compute c, const rt_lattice* lat, const rt_distance_options* opt,
+                                         const uint32_t* occupancy_in, uint32_t* d2, float* distance)
+{
+    return distance_field_entry("rt_terrain_distance_field", c, lat, opt, occupancy_in, nullptr, 0, d2, distance, true);
+}
+
+extern "C" int rt_terrain_distance_field_device(rt_compute c, const rt_lattice* lat, const rt_distance_options* opt,
+                                                const void* occupancy_in_device, void* scratch_device,
+                                                size_t scratch_bytes, void* d2_device, void* distance_device)
+{
+    return distance_field_entry("rt_terrain_distance_field_device", c, lat, opt, occupancy_in_device, scratch_device,
+                                scratch_bytes, d2_device, distance_device, false);
 }
 
 // ---------------------------------------------------------------------------

@@ -909,6 +909,64 @@ class Terrain:
                                                   int(max_triangles), counts_ptr or None)
         return rc == _native.RT_OK
 
+    def distance_field(self, origin, spacing, dims, eye=None, max_cells=0, occupancy=None, squared=False, max_blocks=0):
+        """rt_terrain_distance_field: for every point of the lattice (sample_lattice's origin, spacing and dims) the
+        distance to the nearest lattice point of the other state, formed on the device from the occupancy bits: an
+        array shaped (nz, ny, nx) float32, sqrt(d2) * |spacing|, positive in free space, negative in the ground,
+        +-inf where the lattice has no point of the other state or none within max_cells cells (0: unbounded).  It
+        needs |spacing| equal on the three axes and not 0.  squared: the exact uint32 squared distance in cells^2
+        instead (RT_DIST_FAR for none), for any spacing.  occupancy: None for the terrain's own, or bit words
+        shaped (nz, ny, ceil(nx / 32)) uint32 as sample_lattice returns them (an edited voxel grid); the terrain is
+        not evaluated then.  None if the call fails.  Blocking; uses the camerarays compute."""
+        lat, (nx, ny, nz) = lattice(origin, spacing, dims), (int(v) for v in dims)
+        opt = distance_options(eye, max_cells, max_blocks)
+        occ = None
+        if occupancy is not None:
+            occ = np.ascontiguousarray(occupancy, np.uint32)
+            if occ.size != nz * ny * ((nx + 31) // 32):
+                raise ValueError("distance_field: occupancy must hold ceil(nx / 32) * ny * nz words")
+        self.update_shaders()
+        res = np.empty((nz, ny, nx), np.uint32 if squared else np.float32)
+        rc = lib().rt_terrain_distance_field(self.camera_compute._h, C.byref(lat), C.byref(opt),
+                                             occ.ctypes.data if occ is not None and occ.size else None,
+                                             res.ctypes.data if squared else None, None if squared else res.ctypes.data)
+        return res if rc == _native.RT_OK else None
+
+    def distance_field_device(self, origin, spacing, dims, scratch_ptr, scratch_bytes, d2_ptr=0, distance_ptr=0,
+                              occupancy_ptr=0, eye=None, max_cells=0, max_blocks=0):
+        """rt_terrain_distance_field_device: the same into device arrays -- scratch_ptr at least
+        distance_scratch_bytes(origin, spacing, dims) bytes, d2_ptr nx ny nz uint32 or 0, distance_ptr nx ny nz
+        float32 or 0 (one of the two at least), occupancy_ptr the caller's bit words or 0 for the terrain's own --
+        enqueued on the device's stream with no host synchronisation and no allocation.  True on success."""
+        lat = lattice(origin, spacing, dims)
+        opt = distance_options(eye, max_cells, max_blocks)
+        self.update_shaders()
+        rc = lib().rt_terrain_distance_field_device(self.camera_compute._h, C.byref(lat), C.byref(opt),
+                                                    occupancy_ptr or None, scratch_ptr or None, int(scratch_bytes),
+                                                    d2_ptr or None, distance_ptr or None)
+        return rc == _native.RT_OK
+
+
+def distance_scratch_bytes(origin, spacing, dims):
+    """rt_terrain_distance_scratch_bytes: the bytes of distance_field_device's scratch block for a lattice (0 for an
+    invalid lattice or one without points)."""
+    lat = lattice(origin, spacing, dims)
+    return int(lib().rt_terrain_distance_scratch_bytes(C.byref(lat)))
+
+
+def distance_options(eye=None, max_cells=0, max_blocks=0):
+    """An rt_distance_options block: the eye of the terrain's own occupancy (None: the compute's Eye), the largest
+    distance in cells that stays finite (0: unbounded), the grids' cap."""
+    opt = _native.RtDistanceOptions()
+    opt.size = C.sizeof(_native.RtDistanceOptions)
+    opt.flags = 0
+    if eye is not None:
+        opt.flags |= _native.RT_RAYS_EYE
+        opt.eye[:] = [float(x) for x in np.asarray(eye, np.float32).reshape(3)]
+    opt.max_blocks = int(max_blocks)
+    opt.max_cells = int(max_cells)
+    return opt
+
 
 def mesh_scratch_bytes(origin, spacing, dims):
     """rt_terrain_mesh_scratch_bytes: the bytes of extract_mesh_device's scratch block for a lattice (0 for an

@@ -730,6 +730,60 @@ int rt_terrain_extract_mesh_device(rt_compute cs, const rt_lattice* lat, const r
                                    void* normals_device, uint32_t max_vertices, void* triangles_device,
                                    uint32_t max_triangles, void* counts_device);
 
+/* ---- distance fields (ABI 9, additive; no reference counterpart) ----
+ * How far every point of a lattice is from the terrain's surface, in lattice terms and exactly: the clearance of an
+ * agent of radius r in an occupancy grid, a sphere's collision test, a safe spawn volume, a navigation cost.  The
+ * density is no distance (a noise sum with terraces and a pow); this is one, formed on the device from the
+ * occupancy bits alone, so only the field the caller asks for comes back.
+ * The lattice is an rt_lattice exactly as rt_terrain_sample_lattice reads it.  A point is INSIDE when its occupancy
+ *   bit is set, which for the terrain's own occupancy means getDensity > 0.  For the lattice point p = (ix, iy, iz):
+ *     d2(p) = min over the lattice points q of the same lattice with inside(q) != inside(p)
+ *             of (qx-ix)^2 + (qy-iy)^2 + (qz-iz)^2                     uint32, in cells^2, exact
+ *           = RT_DIST_FAR  when there is no such q (the lattice is all inside or all outside)
+ *                          or, with max_cells = R > 0, when that minimum exceeds R * R
+ *     distance(p) = s * (sqrt((float)d2) * |spacing[0]|), s = +1 outside, -1 inside: one conversion, one correctly
+ *                   rounded square root and one multiply, each rounded to nearest; +-INFINITY for RT_DIST_FAR
+ *   both at index (iz * ny + iy) * nx + ix, as the lattice's results.  The largest finite d2 is 3 * 4095^2 < 2^26, and
+ *   the far value is never added to, so no sum overflows.  d2 is at least 1.
+ * distance is positive in free space and negative in the ground.  The surface crosses the segment from p to its
+ *   nearest q, so |distance| is an UPPER bound of the true clearance, tight to less than one cell diagonal
+ *   (sqrt(3) |spacing|): a caller that needs a safe radius subtracts that.
+ * distance is defined for an isotropic lattice only, |spacing[0]| == |spacing[1]| == |spacing[2]| != 0 (the signs
+ *   may differ); otherwise asking for it is RT_ERR_INVALID.  d2 is a lattice metric and defined for any spacing,
+ *   0 and negative included.
+ * occupancy_in NULL: the terrain's own occupancy, computed on the device as rt_terrain_sample_lattice computes its
+ *   occupancy words (RT_RAYS_EYE and max_blocks as there, either kind of compute), into the scratch block.
+ * occupancy_in not NULL: the caller's words in rt_terrain_sample_lattice's layout, ceil(nx / 32) words per point row,
+ *   bit ix % 32 of word ix / 32; the terrain is not evaluated.  The padding bits of a row's last word are ignored
+ *   whatever they hold.  This is the form for edited voxel grids.
+ * opt (NULL: the defaults) is an rt_distance_options: size >= 28, flags RT_RAYS_EYE or 0, eye, max_blocks (the cap
+ *   of every pass's grid, 0: none), max_cells (0: unbounded).  max_cells bounds the work as well as the answer: a
+ *   lattice that is all inside or all outside, or has wide regions far from any surface, costs a scan of whole
+ *   columns without it.
+ * At least one of d2 and distance is required; a NULL one is not written.
+ * rt_terrain_distance_scratch_bytes: the device form's scratch block for the lattice: its occupancy words, one
+ *   word a point for the x pass and two for the y pass, each part rounded up to 16 bytes; 0 for an invalid lattice
+ *   or one without points.
+ * rt_terrain_distance_field: host arrays; blocking; nothing but the arrays asked for is downloaded.
+ * rt_terrain_distance_field_device: device arrays (4-byte aligned), enqueued on the compute's device stream; it
+ *   allocates nothing and never synchronises the host.  RT_ERR_INVALID when scratch_bytes is below
+ *   rt_terrain_distance_scratch_bytes(lat), and nothing is written.
+ * Both: RT_ERR_INVALID for the lattice's errors (as rt_terrain_sample_lattice), a NULL compute or lattice,
+ *   opt->size < 28, flags other than RT_RAYS_EYE, distance on an anisotropic or zero spacing, d2 and distance both
+ *   NULL.  RT_ERR_STATE without texPerm2D bound, or with the fail-safe word set.  A dims product of 0 is RT_OK and
+ *   launches nothing.  A distance field reads no frame state and changes none: it flushes no deferred frame and
+ *   invalidates no ahead / fused prepass or captured graph, so it may run between any two renders.
+ * Out of scope: sub-cell refinement of the distance from the densities; anisotropic metric distances; trilinear
+ *   sampling of the field at free points; a sphere-sweep query; an eye per point. */
+#define RT_DIST_FAR 0xFFFFFFFFu
+typedef struct { uint32_t size, flags; float eye[3]; uint32_t max_blocks; uint32_t max_cells; } rt_distance_options; /* 28 bytes, v1 */
+size_t rt_terrain_distance_scratch_bytes(const rt_lattice* lat);
+int rt_terrain_distance_field(rt_compute cs, const rt_lattice* lat, const rt_distance_options* opt,
+                              const uint32_t* occupancy_in, uint32_t* d2, float* distance);
+int rt_terrain_distance_field_device(rt_compute cs, const rt_lattice* lat, const rt_distance_options* opt,
+                                     const void* occupancy_in_device, void* scratch_device, size_t scratch_bytes,
+                                     void* d2_device, void* distance_device);
+
 /* ---- diagnostics (primitive-level parity tests; no reference counterpart) ----
  * rt_debug_math: device evaluation of the numeric primitives of DESIGN.md §Numerics
  *   (op 0 exp2, 1 log2, 2 exp, 3 sin, 4 cos, 5 sqrt, 6 rcp, 7 rsqrt, 8 pow, 9 max,
