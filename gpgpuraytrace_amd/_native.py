@@ -83,6 +83,15 @@ class RtDistanceOptions(C.Structure):
                 ("max_cells", C.c_uint32)]
 
 
+RT_PATH_FAR = 0xFFFFFFFF  # the cost of an impassable or unreached point (or one beyond max_cost)
+RT_PATH_NONE = 255  # the flow of a point whose cost is far
+
+
+class RtPathOptions(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("eye", C.c_float * 3), ("max_blocks", C.c_uint32),
+                ("clearance_cells", C.c_uint32), ("max_cost", C.c_uint32), ("max_sweeps", C.c_uint32)]
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -187,6 +196,13 @@ SIGNATURES = {
     "rt_terrain_distance_field": (_i, [_vp, C.POINTER(RtLattice), C.POINTER(RtDistanceOptions), _vp, _vp, _vp]),
     "rt_terrain_distance_field_device": (_i, [_vp, C.POINTER(RtLattice), C.POINTER(RtDistanceOptions), _vp, _vp, _sz,
                                               _vp, _vp]),
+    # path fields: the cheapest 3-4-5 chamfer path cost (uint32) from seed points through the passable points of a
+    # lattice, its first move (uint8) and four status words; the device form takes its scratch block
+    "rt_terrain_path_scratch_bytes": (_sz, [C.POINTER(RtLattice), C.POINTER(RtPathOptions)]),
+    "rt_terrain_path_field": (_i, [_vp, C.POINTER(RtLattice), C.POINTER(RtPathOptions), _vp, _vp, C.c_uint32, _vp, _vp,
+                                   _vp]),
+    "rt_terrain_path_field_device": (_i, [_vp, C.POINTER(RtLattice), C.POINTER(RtPathOptions), _vp, _vp, C.c_uint32,
+                                          _vp, _sz, _vp, _vp, _vp]),
     "rt_noise_generate": (_i, [C.c_uint32, _i, _vp, _vp]),
     "rt_terrain_set_target_depths": (_i, [_vp, _vp]),
     "rt_recorder_create": (_i, [_vp, _i, _i, _cp, C.POINTER(_vp)]),

@@ -266,6 +266,34 @@ struct RtDistanceQuery {
 };
 bool rt_launch_distancequery(const RtLaunch& a, const RtDistanceQuery& q);
 
+// A path field's passes (rt_terrain_path_field; the definition is in include/frosttrace.h, the schedule, the tiles
+// and the scratch layout in rt_rayquery.h).  `stage` chooses what one call enqueues on a.stream:
+//   RT_PATH_INIT:   k_pathinit (passable words from `occupancy` and, if not null, `d2`; cost far; flags, counters and
+//                   status cleared) and k_pathseed (`seeds`, n_seeds of them);
+//   RT_PATH_SWEEP:  `sweeps` launches of k_pathsweep, numbered first_sweep, first_sweep + 1, ...;
+//   RT_PATH_FINISH: k_pathfinish after first_sweep sweeps in all: `flow` (may be null), the reached count, status.
+// flags: two arrays of `tiles` words; counters: rtq::PATH_CNT_WORDS words.  All dims >= 1 with a product of 2^26 at
+// most.  false: nothing launched.
+enum { RT_PATH_INIT = 0, RT_PATH_SWEEP = 1, RT_PATH_FINISH = 2 };
+struct RtPathQuery {
+    int stage;
+    const uint32_t* occupancy;
+    const uint32_t* d2;
+    const uint32_t* seeds;
+    uint32_t n_seeds;
+    uint32_t* passable;
+    uint32_t* flags;
+    uint32_t* counters;
+    uint32_t dims[3];
+    uint32_t limit; // rtq::path_limit
+    uint32_t first_sweep, sweeps;
+    uint32_t* cost;
+    uint8_t* flow;
+    uint32_t* status;
+    uint32_t sweep_blocks, point_blocks;
+};
+bool rt_launch_pathquery(const RtLaunch& a, const RtPathQuery& q);
+
 #define RT_TILE 32
 #define RT_FIN_SLOTS 1536 // k_trace's fin pool slots per block
 #define RT_AO_POOL_SLOTS 256 // k_trace's AO counter slots per block (LDS) and their colours (cpool)

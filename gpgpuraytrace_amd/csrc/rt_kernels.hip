@@ -3437,6 +3437,226 @@ bool rt_launch_distancequery(const RtLaunch& a, const RtDistanceQuery& q)
 }
 
 // ---------------------------------------------------------------------------
+// Path fields (rt_terrain_path_field): the cost of the cheapest 3-4-5 chamfer path from the seeds to every point
+// through the passable points, and its first move (include/frosttrace.h has the definition, rt_rayquery.h the
+// schedule, the tiles, the moves and the scratch layout).  The cost is the least fixed point of an integer
+// relaxation, so the order of the relaxations is free: a sweep launch relaxes every tile marked for it in LDS and
+// marks the neighbours of the tiles it changed for the next launch.  Stream order is the only barrier between
+// sweeps; no workgroup waits on another, and every loop is bounded by a dim, a count or the tile's points.
+namespace {
+
+struct PathGrid {
+    uint32_t nx, ny, nz, points;
+    uint32_t tnx, tny, tnz, tiles;
+    uint32_t limit; // rtq::path_limit: a candidate above it is never stored
+};
+
+__device__ __forceinline__ uint32_t path_words(const PathGrid& g) { return (g.nx + 31u) / 32u; }
+
+// mark tile (tx + dx, ty + dy, tz + dz), if the lattice has it, in `flags`, and count it once in *active
+__device__ __forceinline__ void path_mark(uint32_t* flags, uint32_t* active, const PathGrid& g, uint32_t tx, uint32_t ty,
+                                          uint32_t tz, int dx, int dy, int dz)
+{
+    const uint32_t qx = tx + (uint32_t)dx, qy = ty + (uint32_t)dy, qz = tz + (uint32_t)dz; // below 0 wraps: >= count
+    if (qx >= g.tnx || qy >= g.tny || qz >= g.tnz) return;
+    uint32_t* f = flags + (qz * g.tny + qy) * g.tnx + qx;
+    if (__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+    if (atomicExch(f, 1u) == 0u) atomicAdd(active, 1u);
+}
+
+// the passable words (not blocked, a point that exists, and with a clearance a far d2), every cost far, the tile
+// flags, the counters and the status cleared
+__global__ void __launch_bounds__(rtq::kDistThreads) k_pathinit(const uint32_t* __restrict__ occ, const uint32_t* __restrict__ d2,
+                                                               uint32_t* __restrict__ passable, uint32_t* __restrict__ cost,
+                                                               uint32_t* __restrict__ flags, uint32_t* counters, uint32_t* status,
+                                                               PathGrid g)
+{
+    const uint32_t words = path_words(g), all_words = words * g.ny * g.nz;
+    const uint32_t first = blockIdx.x * rtq::kDistThreads + threadIdx.x, stride = gridDim.x * rtq::kDistThreads;
+    for (uint32_t i = first; i < g.points; i += stride) cost[i] = rtq::kPathFar;
+    for (uint32_t i = first; i < 2u * g.tiles; i += stride) flags[i] = 0u;
+    if (first < (uint32_t)rtq::PATH_CNT_WORDS) counters[first] = 0u;
+    if (first < 4u) status[first] = 0u;
+    for (uint32_t w = first; w < all_words; w += stride) {
+        const uint32_t row = w / words, j = w - row * words;
+        uint32_t open = ~occ[w] & rtq::dist_valid_bits(g.nx, j);
+        if (d2) {
+            const uint32_t* __restrict__ r = d2 + (size_t)row * g.nx + 32u * j;
+            const uint32_t seen = open;
+            for (uint32_t b = 0; b < 32u; ++b)
+                if (((seen >> b) & 1u) && r[b] != rtq::kDistFar) open &= ~(1u << b);
+        }
+        passable[w] = open;
+    }
+}
+
+// the seeds: cost 0 at the passable ones, their tile and its neighbours marked for sweep 0
+__global__ void __launch_bounds__(rtq::kDistThreads) k_pathseed(const uint32_t* __restrict__ seeds, uint32_t n_seeds,
+                                                               const uint32_t* __restrict__ passable, uint32_t* __restrict__ cost,
+                                                               uint32_t* flags, uint32_t* counters, PathGrid g)
+{
+    const uint32_t words = path_words(g);
+    for (uint32_t i = blockIdx.x * rtq::kDistThreads + threadIdx.x; i < n_seeds; i += gridDim.x * rtq::kDistThreads) {
+        const uint32_t s = seeds[i];
+        if (s >= g.points) continue;
+        const uint32_t row = s / g.nx, ix = s - row * g.nx, iy = row % g.ny, iz = row / g.ny;
+        if (!((passable[(size_t)row * words + (ix >> 5)] >> (ix & 31u)) & 1u)) continue;
+        cost[s] = 0u;
+        for (int dz = -1; dz <= 1; ++dz)
+            for (int dy = -1; dy <= 1; ++dy)
+                for (int dx = -1; dx <= 1; ++dx)
+                    path_mark(flags, counters + rtq::PATH_CNT_ACTIVE, g, ix / rtq::kPathTileX, iy / rtq::kPathTileY,
+                              iz / rtq::kPathTileZ, dx, dy, dz);
+    }
+}
+
+// One sweep.  A block strides over the tiles and takes those marked for this sweep: the tile's costs with a
+// one-point halo into LDS, the 26 moves relaxed there (a thread a point) until no point of the tile falls, the
+// points that fell stored, and the neighbouring tiles marked for the next sweep.  Only this block stores the
+// tile's points; a halo cost read while its owner lowers it is still the cost of a real path, and the owner's
+// mark brings this tile back in the next sweep.
+__global__ void __launch_bounds__(rtq::kPathTilePoints) k_pathsweep(uint32_t* cost, const uint32_t* __restrict__ passable,
+                                                                   uint32_t* flags, uint32_t* counters, uint32_t sweep, PathGrid g)
+{
+    __shared__ uint32_t c[rtq::kPathHaloPoints];
+    const uint32_t tid = threadIdx.x;
+    uint32_t* cur = flags + (sweep & 1u) * g.tiles;
+    uint32_t* next = flags + ((sweep + 1u) & 1u) * g.tiles;
+    uint32_t* active = counters + rtq::PATH_CNT_ACTIVE;
+    if (blockIdx.x == 0 && tid == 0) {
+        active[(sweep + 2u) % 3u] = 0u;
+        counters[rtq::PATH_CNT_WORKED + ((sweep + 1u) & 1u)] = 0u;
+    }
+    if (active[sweep % 3u] == 0u) return; // nothing marked for this sweep
+    const uint32_t words = path_words(g);
+    const uint32_t lx = tid % rtq::kPathTileX, ly = tid / rtq::kPathTileX % rtq::kPathTileY,
+                   lz = tid / (rtq::kPathTileX * rtq::kPathTileY);
+    const uint32_t me = ((lz + 1u) * rtq::kPathHaloY + ly + 1u) * rtq::kPathHaloX + lx + 1u;
+    for (uint32_t t = blockIdx.x; t < g.tiles; t += gridDim.x) {
+        if (cur[t] == 0u) continue; // (the same for the whole block)
+        const uint32_t tx = t % g.tnx, ty = t / g.tnx % g.tny, tz = t / (g.tnx * g.tny);
+        const uint32_t x0 = tx * rtq::kPathTileX, y0 = ty * rtq::kPathTileY, z0 = tz * rtq::kPathTileZ;
+        for (uint32_t h = tid; h < rtq::kPathHaloPoints; h += rtq::kPathTilePoints) {
+            const uint32_t hx = h % rtq::kPathHaloX, hy = h / rtq::kPathHaloX % rtq::kPathHaloY,
+                           hz = h / (rtq::kPathHaloX * rtq::kPathHaloY);
+            const uint32_t qx = x0 + hx - 1u, qy = y0 + hy - 1u, qz = z0 + hz - 1u; // below 0 wraps: >= dim
+            uint32_t v = rtq::kPathFar;
+            if (qx < g.nx && qy < g.ny && qz < g.nz) v = cost[((size_t)qz * g.ny + qy) * g.nx + qx];
+            c[h] = v;
+        }
+        const uint32_t ix = x0 + lx, iy = y0 + ly, iz = z0 + lz;
+        const bool exists = ix < g.nx && iy < g.ny && iz < g.nz;
+        const size_t row = (size_t)iz * g.ny + iy;
+        const bool open = exists && ((passable[row * words + tx] >> lx) & 1u);
+        __syncthreads();
+        if (tid == 0) {
+            cur[t] = 0u;
+            atomicAdd(counters + rtq::PATH_CNT_VISITS, 1u);
+        }
+        const uint32_t before = c[me];
+        uint32_t mine = before;
+        bool settled = false;
+        for (uint32_t pass = 0; pass < rtq::kPathTilePoints; ++pass) {
+            uint32_t best = mine;
+            if (open) {
+#pragma unroll
+                for (int dz = -1; dz <= 1; ++dz)
+#pragma unroll
+                    for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+                        for (int dx = -1; dx <= 1; ++dx) {
+                            if (!dx && !dy && !dz) continue;
+                            const uint32_t v = c[(int)me + (dz * (int)rtq::kPathHaloY + dy) * (int)rtq::kPathHaloX + dx];
+                            const uint32_t cand = v + rtq::path_weight(dx, dy, dz);
+                            if (v != rtq::kPathFar && cand < best) best = cand; // (far is never added to)
+                        }
+            }
+            const bool lower = best < mine && best <= g.limit;
+            if (!__syncthreads_or(lower)) {
+                settled = true;
+                break;
+            }
+            if (lower) c[me] = mine = best;
+            __syncthreads();
+        }
+        const bool changed = mine != before;
+        if (changed) cost[row * g.nx + ix] = mine;
+        if (__syncthreads_or(changed)) {
+            // the tile itself again only if the bound ended the loop before the local fixed point
+            if (tid < 27u && (tid != rtq::kPathStay || !settled)) {
+                int dx, dy, dz;
+                rtq::path_move(tid, &dx, &dy, &dz);
+                path_mark(next, active + (sweep + 1u) % 3u, g, tx, ty, tz, dx, dy, dz);
+            }
+            if (tid == 32u && atomicExch(counters + rtq::PATH_CNT_WORKED + (sweep & 1u), 1u) == 0u)
+                atomicAdd(counters + rtq::PATH_CNT_SWEEPS, 1u);
+        }
+    }
+}
+
+// the flow, the reached points (a wave reduction, an atomic a wave) and the status, after `sweeps` sweeps
+__global__ void __launch_bounds__(rtq::kDistThreads) k_pathfinish(const uint32_t* __restrict__ cost, uint8_t* __restrict__ flow,
+                                                                 const uint32_t* counters, uint32_t* status,
+                                                                 uint32_t sweeps, PathGrid g)
+{
+    const uint32_t dims[3] = {g.nx, g.ny, g.nz};
+    uint32_t reached = 0u;
+    for (uint32_t i = blockIdx.x * rtq::kDistThreads + threadIdx.x; i < g.points; i += gridDim.x * rtq::kDistThreads) {
+        const uint32_t v = cost[i];
+        reached += v != rtq::kPathFar;
+        if (!flow) continue;
+        uint32_t f = v == rtq::kPathFar ? rtq::kPathNone : rtq::kPathStay;
+        if (v != rtq::kPathFar && v != 0u) {
+            const uint32_t row = i / g.nx;
+            f = rtq::path_flow([&](uint32_t q) { return cost[q]; }, dims, i - row * g.nx, row % g.ny, row / g.ny, v);
+        }
+        flow[i] = (uint8_t)f;
+    }
+    for (int off = 32; off > 0; off >>= 1) reached += __shfl_down(reached, off, 64);
+    if ((threadIdx.x & 63u) == 0u && reached) atomicAdd(status + 2, reached);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        status[0] = counters[rtq::PATH_CNT_ACTIVE + sweeps % 3u] == 0u ? 1u : 0u;
+        status[1] = counters[rtq::PATH_CNT_SWEEPS];
+        status[3] = 0u;
+    }
+}
+
+} // namespace
+
+bool rt_launch_pathquery(const RtLaunch& a, const RtPathQuery& q)
+{
+    const uint64_t points = (uint64_t)q.dims[0] * q.dims[1] * q.dims[2];
+    if (points == 0 || points > (1u << 26) || q.sweep_blocks == 0 || q.point_blocks == 0) return false;
+    if (q.dims[0] > rtq::kMaxLatticeDim || q.dims[1] > rtq::kMaxLatticeDim || q.dims[2] > rtq::kMaxLatticeDim) return false;
+    if (!q.passable || !q.flags || !q.counters || !q.cost || !q.status) return false;
+    const rtq::PathTiles t = rtq::path_tiles(q.dims);
+    const PathGrid g{q.dims[0], q.dims[1], q.dims[2], (uint32_t)points, t.n[0], t.n[1], t.n[2], t.total, q.limit};
+    const dim3 pgrid(q.point_blocks), pblock(rtq::kDistThreads);
+    switch (q.stage) {
+    case RT_PATH_INIT: {
+        if (!q.occupancy || !q.seeds || q.n_seeds == 0 || q.n_seeds > rtq::kPathMaxSeeds) return false;
+        hipLaunchKernelGGL(k_pathinit, pgrid, pblock, 0, a.stream, q.occupancy, q.d2, q.passable, q.cost, q.flags, q.counters,
+                           q.status, g);
+        const uint32_t need = (q.n_seeds + rtq::kDistThreads - 1u) / rtq::kDistThreads;
+        hipLaunchKernelGGL(k_pathseed, dim3(need < q.point_blocks ? need : q.point_blocks), pblock, 0, a.stream, q.seeds,
+                           q.n_seeds, q.passable, q.cost, q.flags, q.counters, g);
+        return true;
+    }
+    case RT_PATH_SWEEP:
+        if (q.sweeps == 0 || q.sweeps > rtq::kPathMaxSweeps) return false;
+        for (uint32_t k = 0; k < q.sweeps; ++k)
+            hipLaunchKernelGGL(k_pathsweep, dim3(q.sweep_blocks), dim3(rtq::kPathTilePoints), 0, a.stream, q.cost, q.passable,
+                               q.flags, q.counters, q.first_sweep + k, g);
+        return true;
+    case RT_PATH_FINISH:
+        hipLaunchKernelGGL(k_pathfinish, pgrid, pblock, 0, a.stream, q.cost, q.flow, q.counters, q.status, q.first_sweep, g);
+        return true;
+    default:
+        return false;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Diagnostics: device evaluation of the numeric primitives, noise3d and
 // getDensity for the primitive-level parity tests (tests/test_gpu_parity.py).
 namespace {

@@ -4,7 +4,8 @@
 // its lanes per ray, its strips and its grid, the layout of the host forms' device block, and the scratch layout,
 // grids and mask arithmetic of rt_terrain_extract_mesh.  No HIP in here (the mask arithmetic is marked
 // __host__ __device__ under hipcc only, for k_meshcount): tests/tools/rayquery_check.cpp, surfquery_check.cpp,
-// shadequery_check.cpp, pointquery_check.cpp, fieldquery_check.cpp, meshquery_check.cpp and querylayout_check.cpp
+// shadequery_check.cpp, pointquery_check.cpp, fieldquery_check.cpp, meshquery_check.cpp, distquery_check.cpp,
+// pathquery_check.cpp and querylayout_check.cpp
 // drive it stand-alone under ASan + UBSan.
 #pragma once
 
@@ -697,6 +698,162 @@ inline DistancePlan plan_distance(uint32_t points, uint32_t max_blocks, int cus)
 {
     DistancePlan p;
     p.blocks = field_grid((points + kDistThreads - 1u) / kDistThreads, max_blocks, 8 * (cus > 0 ? cus : 1));
+    return p;
+}
+
+// ---- path fields (rt_terrain_path_field): the cheapest 3-4-5 chamfer path from seeds through passable points ----
+//
+// The cost is the least fixed point of cost(p) = min(cost(p), cost(q) + w(p - q)) over the 26 neighbours q, so the
+// kernels may relax in any order.  k_pathinit forms the passable words (not blocked, and with a clearance d2 far),
+// sets every cost far and clears the tile flags and counters; k_pathseed sets the passable seeds to 0 and marks
+// their tiles; each k_pathsweep launch relaxes the tiles marked for it to their local fixed point in LDS and marks
+// the neighbours of the tiles that changed for the next launch; k_pathfinish writes the flow, counts the reached
+// points and writes the status.
+
+constexpr uint32_t kPathFar = 0xffffffffu; // RT_PATH_FAR
+constexpr uint32_t kPathNone = 255u;       // RT_PATH_NONE
+constexpr uint32_t kPathStay = 13u;        // the move code of (0, 0, 0)
+// the first version of rt_path_options: size, flags, eye[3], max_blocks, clearance_cells, max_cost, max_sweeps
+constexpr uint32_t kPathOptSizeV1 = 36u;
+constexpr uint32_t kPathMaxClearance = 4095u;
+constexpr uint32_t kPathMaxSeeds = 1u << 26;
+constexpr uint32_t kPathMaxSweeps = 4096u; // of the device form
+constexpr uint32_t kPathBatch = 16u;       // sweeps between two looks of the host form at the active counter
+
+struct PathOptions : Options {
+    uint32_t clearance_cells = 0, max_cost = 0, max_sweeps = 0;
+};
+
+// `opt` is the caller's rt_path_options (may be null: the defaults), read as far as the first version reaches.
+inline int parse_path_options(const void* opt, PathOptions* out, const char** why)
+{
+    *out = PathOptions{};
+    if (!opt) return OK;
+    if (!parse_prefix(opt, kPathOptSizeV1, out)) {
+        *why = "rt_path_options.size is smaller than the struct's first version";
+        return INVALID;
+    }
+    if (out->flags & ~kEye) {
+        *why = "rt_path_options.flags has bits other than RT_RAYS_EYE";
+        return INVALID;
+    }
+    const char* p = static_cast<const char*>(opt);
+    std::memcpy(&out->clearance_cells, p + 24, 4);
+    std::memcpy(&out->max_cost, p + 28, 4);
+    std::memcpy(&out->max_sweeps, p + 32, 4);
+    if (out->clearance_cells > kPathMaxClearance) {
+        *why = "rt_path_options.clearance_cells is above 4095";
+        return INVALID;
+    }
+    return OK;
+}
+
+// the largest cost that is stored: max_cost, or without one everything below the far value (a finite cost is below
+// 5 * 2^26, far below it)
+inline uint32_t path_limit(uint32_t max_cost) { return max_cost ? max_cost : kPathFar - 1u; }
+
+// The moves: code c = (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1), 0..26, 13 is "stay".
+RTQ_HD inline void path_move(uint32_t c, int* dx, int* dy, int* dz)
+{
+    *dx = (int)(c % 3u) - 1;
+    *dy = (int)(c / 3u % 3u) - 1;
+    *dz = (int)(c / 9u) - 1;
+}
+// 3 for a face move, 4 for an edge move, 5 for a corner move (the 3-4-5 chamfer, thirds of a cell); 0 for "stay"
+RTQ_HD inline uint32_t path_weight(int dx, int dy, int dz)
+{
+    const uint32_t k = (uint32_t)(dx != 0) + (uint32_t)(dy != 0) + (uint32_t)(dz != 0);
+    return k ? 2u + k : 0u;
+}
+
+// The flow of a point of finite cost `cost` > 0 at (ix, iy, iz): the smallest move code c whose neighbour q is a
+// lattice point with cost(q) + w(c) == cost; kPathNone when there is none (an unconverged field).  at(i): the cost
+// of point i.  The far value is never added to.
+template <class At>
+RTQ_HD inline uint32_t path_flow(At at, const uint32_t dims[3], uint32_t ix, uint32_t iy, uint32_t iz, uint32_t cost)
+{
+    for (uint32_t c = 0; c < 27u; ++c) {
+        if (c == kPathStay) continue;
+        int dx, dy, dz;
+        path_move(c, &dx, &dy, &dz);
+        const uint32_t qx = ix + (uint32_t)dx, qy = iy + (uint32_t)dy, qz = iz + (uint32_t)dz; // below 0 wraps: >= dim
+        if (qx >= dims[0] || qy >= dims[1] || qz >= dims[2]) continue;
+        const uint32_t v = at((qz * dims[1] + qy) * dims[0] + qx);
+        if (v != kPathFar && v + path_weight(dx, dy, dz) == cost) return c;
+    }
+    return kPathNone;
+}
+
+// The tiles: 32 x 4 x 4 points, an x run of a tile is one occupancy word.  Tile index (tz * ty_n + ty) * tx_n + tx.
+constexpr uint32_t kPathTileX = 32u, kPathTileY = 4u, kPathTileZ = 4u;
+constexpr uint32_t kPathTilePoints = kPathTileX * kPathTileY * kPathTileZ; // a thread a point
+// the tile with its one-point halo, as the sweep holds it in LDS
+constexpr uint32_t kPathHaloX = kPathTileX + 2u, kPathHaloY = kPathTileY + 2u, kPathHaloZ = kPathTileZ + 2u;
+constexpr uint32_t kPathHaloPoints = kPathHaloX * kPathHaloY * kPathHaloZ;
+
+struct PathTiles {
+    uint32_t n[3] = {0, 0, 0};
+    uint32_t total = 0;
+};
+// dims all >= 1
+RTQ_HD inline PathTiles path_tiles(const uint32_t dims[3])
+{
+    PathTiles t;
+    t.n[0] = (dims[0] + kPathTileX - 1u) / kPathTileX;
+    t.n[1] = (dims[1] + kPathTileY - 1u) / kPathTileY;
+    t.n[2] = (dims[2] + kPathTileZ - 1u) / kPathTileZ;
+    t.total = t.n[0] * t.n[1] * t.n[2];
+    return t;
+}
+RTQ_HD inline uint32_t path_tile_of(const PathTiles& t, uint32_t ix, uint32_t iy, uint32_t iz)
+{
+    return ((iz / kPathTileZ) * t.n[1] + iy / kPathTileY) * t.n[0] + ix / kPathTileX;
+}
+
+// the counters of a path field, the last part of its scratch block (uint32 each)
+enum {
+    PATH_CNT_ACTIVE = 0, // [3]: sweep k reads [k % 3], the tiles marked for it, counts into [(k + 1) % 3], clears [(k + 2) % 3]
+    PATH_CNT_WORKED = 3, // [2]: sweep k sets [k & 1] once a tile of it changed, and clears [(k + 1) & 1]
+    PATH_CNT_SWEEPS = 5, // sweeps in which a tile changed
+    PATH_CNT_VISITS = 6, // active tiles visited
+    PATH_CNT_WORDS = 16
+};
+
+// The scratch block of a path field, laid out by block_layout: the lattice's occupancy words (used when the
+// terrain's own occupancy is asked for); with a clearance the distance field's scratch block followed by its d2, a
+// uint32 a point; the passable words; the two tile flag arrays, a uint32 a tile each; the counters.
+struct PathScratch {
+    uint32_t points = 0;
+    PathTiles tiles;
+    size_t d2_offset = 0; // of d2 within the PATH_DISTANCE part
+    BlockLayout lay;      // total 0 without points
+};
+enum { PATH_OCCUPANCY = 0, PATH_DISTANCE = 1, PATH_PASSABLE = 2, PATH_FLAGS = 3, PATH_COUNTERS = 4 };
+
+// dims of a lattice that check_lattice passed
+inline PathScratch path_scratch(const uint32_t dims[3], uint32_t clearance_cells)
+{
+    PathScratch s;
+    s.points = dims[0] * dims[1] * dims[2];
+    if (s.points == 0) return s;
+    s.tiles = path_tiles(dims);
+    s.d2_offset = clearance_cells ? distance_scratch(dims).lay.total : 0;
+    const size_t bytes[5] = {occupancy_bytes(dims), clearance_cells ? s.d2_offset + (size_t)s.points * 4 : 0,
+                             occupancy_bytes(dims), (size_t)s.tiles.total * 8, (size_t)PATH_CNT_WORDS * 4};
+    s.lay = block_layout(bytes, 5);
+    return s;
+}
+
+// The grids: the sweep a block of kPathTilePoints threads a tile, striding over the tile flags, four blocks a CU
+// resident; the point passes (init, finish) as the distance passes.
+struct PathPlan {
+    uint32_t sweep_blocks = 0, point_blocks = 0;
+};
+inline PathPlan plan_path(const PathScratch& s, uint32_t max_blocks, int cus)
+{
+    PathPlan p;
+    p.sweep_blocks = field_grid(s.tiles.total, max_blocks, 4 * (cus > 0 ? cus : 1));
+    p.point_blocks = plan_distance(s.points, max_blocks, cus).blocks;
     return p;
 }
 

@@ -3628,6 +3628,168 @@ extern "C" int rt_terrain_distance_field_device(rt_compute c, const rt_lattice* 
 }
 
 // ---------------------------------------------------------------------------
+// rt_terrain_path_field: the cost of the cheapest chamfer path from the seeds through the passable points, and its
+// first move (include/frosttrace.h): the caller's occupancy words, or the lattice query's occupancy pass into the
+// scratch block; with a clearance the distance passes; then the initialisation, the sweeps and the finish pass
+// (rt_launch_pathquery), all on the device stream.
+namespace {
+
+// the host form keeps its status words behind the counters the kernels use
+constexpr size_t kPathHostStatus = 8;
+static_assert(kPathHostStatus + 4 <= (size_t)rtq::PATH_CNT_WORDS, "the status words lie within the counters' part");
+
+// Enqueue one path field; the scratch block holds s.lay.total bytes; occupancy null: the terrain's own.  The device
+// form (host false) enqueues exactly o.max_sweeps sweeps and never synchronises.  The host form sweeps in batches
+// and reads the count of tiles marked for the next sweep after each, until it is 0 or max_sweeps (if not 0) is
+// reached; status null there: its words stay in the scratch block.
+int path_field_enqueue(rt_compute c, const rtq::Lattice& l, const rtq::PathScratch& s, const rtq::PathOptions& o,
+                       const void* occupancy, const void* seeds, uint32_t n_seeds, char* scratch, void* cost, void* flow,
+                       void* status, bool host)
+{
+    rt_device dev = c->dev;
+    if (!occupancy) {
+        rtq::FieldOptions occ_opt = o; // the eye and the grid's cap
+        void* own = scratch + s.lay.offset[rtq::PATH_OCCUPANCY];
+        if (int rc = sample_field_enqueue(c, nullptr, &l, s.points, occ_opt, nullptr, own)) return rc;
+        occupancy = own;
+    }
+    const RtLaunch a = make_launch(dev, c->shader);
+    const uint32_t* d2 = nullptr;
+    if (o.clearance_cells) {
+        // the distance field's own passes, unchanged, with max_cells the clearance: passable is a far d2
+        char* part = scratch + s.lay.offset[rtq::PATH_DISTANCE];
+        const rtq::DistanceScratch ds = rtq::distance_scratch(l.dims);
+        RtDistanceQuery dq{};
+        dq.occupancy = (const uint32_t*)occupancy;
+        dq.rows = (uint32_t*)(part + ds.lay.offset[rtq::DIST_ROWS]);
+        dq.planes = (uint32_t*)(part + ds.lay.offset[rtq::DIST_PLANES]);
+        memcpy(dq.dims, l.dims, sizeof(dq.dims));
+        const rtq::DistanceBound b = rtq::distance_bound(o.clearance_cells);
+        dq.reach = b.reach;
+        dq.limit2 = b.limit2;
+        dq.d2 = (uint32_t*)(part + s.d2_offset);
+        dq.blocks = rtq::plan_distance(s.points, o.max_blocks, cus_of(dev)).blocks;
+        if (int rc = query_launched(rt_launch_distancequery(a, dq), "rt_terrain_path_field: no kernel for the clearance")) return rc;
+        d2 = dq.d2;
+    }
+    const rtq::PathPlan plan = rtq::plan_path(s, o.max_blocks, cus_of(dev));
+    uint32_t* counters = (uint32_t*)(scratch + s.lay.offset[rtq::PATH_COUNTERS]);
+    RtPathQuery q{};
+    q.occupancy = (const uint32_t*)occupancy;
+    q.d2 = d2;
+    q.seeds = (const uint32_t*)seeds;
+    q.n_seeds = n_seeds;
+    q.passable = (uint32_t*)(scratch + s.lay.offset[rtq::PATH_PASSABLE]);
+    q.flags = (uint32_t*)(scratch + s.lay.offset[rtq::PATH_FLAGS]);
+    q.counters = counters;
+    memcpy(q.dims, l.dims, sizeof(q.dims));
+    q.limit = rtq::path_limit(o.max_cost);
+    q.cost = (uint32_t*)cost;
+    q.flow = (uint8_t*)flow;
+    q.status = host ? counters + kPathHostStatus : (uint32_t*)status;
+    q.sweep_blocks = plan.sweep_blocks;
+    q.point_blocks = plan.point_blocks;
+    const char* no_kernel = "rt_terrain_path_field: no kernel for this query";
+    q.stage = RT_PATH_INIT;
+    if (int rc = query_launched(rt_launch_pathquery(a, q), no_kernel)) return rc;
+    uint32_t done = 0;
+    q.stage = RT_PATH_SWEEP;
+    for (;;) {
+        uint32_t batch = host ? rtq::kPathBatch : o.max_sweeps;
+        if (o.max_sweeps && batch > o.max_sweeps - done) batch = o.max_sweeps - done;
+        q.first_sweep = done;
+        q.sweeps = batch;
+        if (int rc = query_launched(rt_launch_pathquery(a, q), no_kernel)) return rc;
+        done += batch;
+        if (!host || (o.max_sweeps && done >= o.max_sweeps)) break;
+        uint32_t active = 0; // the tiles marked for sweep `done`
+        HIP_TRY(hipMemcpyAsync(&active, counters + rtq::PATH_CNT_ACTIVE + done % 3u, 4, hipMemcpyDeviceToHost, dev->stream));
+        HIP_TRY(hipStreamSynchronize(dev->stream));
+        if (!active) break;
+    }
+    q.stage = RT_PATH_FINISH;
+    q.first_sweep = done;
+    if (int rc = query_launched(rt_launch_pathquery(a, q), no_kernel)) return rc;
+    if (host && status) HIP_TRY(hipMemcpyAsync(status, q.status, 16, hipMemcpyDeviceToHost, dev->stream));
+    return RT_OK;
+}
+
+// both entry points; host: the blocking form, whose arrays are the host's
+int path_field_entry(const char* who, rt_compute c, const rt_lattice* lat, const rt_path_options* opt, const void* occupancy,
+                     const void* seeds, uint32_t n_seeds, void* scratch, size_t scratch_bytes, void* cost, void* flow,
+                     void* status, bool host)
+{
+    const QueryFamily<rtq::PathOptions> f{who, nullptr, rtq::parse_path_options};
+    rtq::Lattice l;
+    rtq::PathScratch s;
+    std::string missing = std::string(who) + (host ? ": seeds or cost is null" : ": seeds, cost or status is null");
+    return query_entry(
+        c, f, 0, opt,
+        [&](const rtq::PathOptions& o, uint32_t* n) -> int {
+            const char* why = "";
+            if (int rc = rtq::check_lattice(lat, &l, n, &why)) return fail(rc, "%s: %s", who, why);
+            s = rtq::path_scratch(l.dims, o.clearance_cells);
+            if (n_seeds < 1u || n_seeds > rtq::kPathMaxSeeds) return fail(RT_ERR_INVALID, "%s: n_seeds must be 1..2^26", who);
+            if (!host && (o.max_sweeps < 1u || o.max_sweeps > rtq::kPathMaxSweeps))
+                return fail(RT_ERR_INVALID, "%s: max_sweeps must be 1..4096", who);
+            if (host && seeds && *n) {
+                const uint32_t* sd = (const uint32_t*)seeds;
+                for (uint32_t i = 0; i < n_seeds; ++i)
+                    if (sd[i] >= *n) return fail(RT_ERR_INVALID, "%s: seed %u is not a point of the lattice", who, i);
+            }
+            if (!host && *n) {
+                if (!scratch || scratch_bytes < s.lay.total)
+                    return fail(RT_ERR_INVALID, "%s: the scratch block is null or below rt_terrain_path_scratch_bytes", who);
+                if (((uintptr_t)scratch | (uintptr_t)occupancy | (uintptr_t)seeds | (uintptr_t)cost | (uintptr_t)status) % 4)
+                    return fail(RT_ERR_INVALID, "%s: the device arrays must be 4-byte aligned", who);
+            }
+            return RT_OK;
+        },
+        !seeds || !cost || (!host && !status) ? missing.c_str() : nullptr,
+        [&](const rtq::PathOptions& o, uint32_t n) {
+            if (!host)
+                return path_field_enqueue(c, l, s, o, occupancy, seeds, n_seeds, (char*)scratch, cost, flow, status, false);
+            // one device block: the scratch, the caller's occupancy words, the seeds, the two results
+            const HostPart parts[] = {{s.lay.total, nullptr, nullptr},
+                                      {occupancy ? rtq::occupancy_bytes(l.dims) : 0, occupancy, nullptr},
+                                      {(size_t)n_seeds * 4, seeds, nullptr},
+                                      {(size_t)n * 4, nullptr, cost},
+                                      {flow ? (size_t)n : 0, nullptr, flow}};
+            return host_form(c->dev, parts, [&](char* const* at) {
+                return path_field_enqueue(c, l, s, o, at[1], at[2], n_seeds, at[0], at[3], at[4], status, true);
+            });
+        });
+}
+
+} // namespace
+
+extern "C" size_t rt_terrain_path_scratch_bytes(const rt_lattice* lat, const rt_path_options* opt)
+{
+    rtq::Lattice l;
+    rtq::PathOptions o;
+    uint32_t n = 0;
+    const char* why = "";
+    if (rtq::check_lattice(lat, &l, &n, &why) || rtq::parse_path_options(opt, &o, &why)) return 0;
+    return rtq::path_scratch(l.dims, o.clearance_cells).lay.total;
+}
+
+extern "C" int rt_terrain_path_field(rt_compute c, const rt_lattice* lat, const rt_path_options* opt, const uint32_t* occupancy_in,
+                                     const uint32_t* seeds, uint32_t n_seeds, uint32_t* cost, uint8_t* flow, uint32_t status[4])
+{
+    return path_field_entry("rt_terrain_path_field", c, lat, opt, occupancy_in, seeds, n_seeds, nullptr, 0, cost, flow, status,
+                            true);
+}
+
+extern "C" int rt_terrain_path_field_device(rt_compute c, const rt_lattice* lat, const rt_path_options* opt,
+                                            const void* occupancy_in_device, const void* seeds_device, uint32_t n_seeds,
+                                            void* scratch_device, size_t scratch_bytes, void* cost_device, void* flow_device,
+                                            void* status_device)
+{
+    return path_field_entry("rt_terrain_path_field_device", c, lat, opt, occupancy_in_device, seeds_device, n_seeds,
+                            scratch_device, scratch_bytes, cost_device, flow_device, status_device, false);
+}
+
+// ---------------------------------------------------------------------------
 // rt_readback_*: the asynchronous readback ring (struct rt_readback_s above; include/frosttrace.h)
 int rt_readback_create(rt_device d, int format, int depth, rt_readback* out)
 {

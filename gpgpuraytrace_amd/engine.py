@@ -946,6 +946,124 @@ class Terrain:
                                                     d2_ptr or None, distance_ptr or None)
         return rc == _native.RT_OK
 
+    def path_field(self, origin, spacing, dims, seeds, eye=None, clearance=0, occupancy=None, max_cost=0, flow=False,
+                   max_sweeps=0, max_blocks=0, status=None):
+        """rt_terrain_path_field: for every point of the lattice (sample_lattice's origin, spacing and dims) the cost
+        of the cheapest path from the seeds through the passable points, an array shaped (nz, ny, nx) uint32 in
+        thirds of a cell (a face move 3, an edge move 4, a corner move 5; world length cost * |spacing| / 3),
+        RT_PATH_FAR where a point is blocked, unreachable or beyond max_cost (0: unbounded).  seeds: (n, 3) ix, iy,
+        iz, or flat point indices.  clearance: passable points are more than that many cells from every blocked
+        point.  occupancy: None for the terrain's own, or bit words as sample_lattice returns them.  flow=True:
+        (cost, flow), flow uint8 the move code (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1) of the first step back to a
+        seed, 13 at a seed, RT_PATH_NONE where the cost is far.  max_sweeps 0: until converged.  status: a list
+        that receives the four status words.  None if the call fails.  Blocking; uses the camerarays compute."""
+        lat, (nx, ny, nz) = lattice(origin, spacing, dims), (int(v) for v in dims)
+        opt = path_options(eye, clearance, max_cost, max_sweeps, max_blocks)
+        occ = None
+        if occupancy is not None:
+            occ = np.ascontiguousarray(occupancy, np.uint32)
+            if occ.size != nz * ny * ((nx + 31) // 32):
+                raise ValueError("path_field: occupancy must hold ceil(nx / 32) * ny * nz words")
+        sd = seed_indices(seeds, (nx, ny, nz))
+        self.update_shaders()
+        cost = np.empty((nz, ny, nx), np.uint32)
+        fl = np.empty((nz, ny, nx), np.uint8) if flow else None
+        st = np.zeros(4, np.uint32)
+        rc = lib().rt_terrain_path_field(self.camera_compute._h, C.byref(lat), C.byref(opt),
+                                         occ.ctypes.data if occ is not None and occ.size else None,
+                                         sd.ctypes.data if sd.size else None, int(sd.size),
+                                         cost.ctypes.data, fl.ctypes.data if flow and fl.size else None, st.ctypes.data)
+        if rc != _native.RT_OK:
+            return None
+        if status is not None:
+            status[:] = [int(v) for v in st]
+        return (cost, fl) if flow else cost
+
+    def path_field_device(self, origin, spacing, dims, seeds_ptr, n_seeds, scratch_ptr, scratch_bytes, cost_ptr,
+                          status_ptr, flow_ptr=0, occupancy_ptr=0, eye=None, clearance=0, max_cost=0, max_sweeps=1,
+                          max_blocks=0):
+        """rt_terrain_path_field_device: the same into device arrays -- seeds_ptr n_seeds uint32 point indices,
+        scratch_ptr at least path_scratch_bytes(origin, spacing, dims, clearance) bytes, cost_ptr nx ny nz uint32,
+        status_ptr 4 uint32, flow_ptr nx ny nz uint8 or 0, occupancy_ptr the caller's bit words or 0 for the
+        terrain's own -- an initialisation, exactly max_sweeps (1..4096) sweeps and a finish pass enqueued on the
+        device's stream with no host synchronisation and no allocation.  True on success."""
+        lat = lattice(origin, spacing, dims)
+        opt = path_options(eye, clearance, max_cost, max_sweeps, max_blocks)
+        self.update_shaders()
+        rc = lib().rt_terrain_path_field_device(self.camera_compute._h, C.byref(lat), C.byref(opt), occupancy_ptr or None,
+                                                seeds_ptr or None, int(n_seeds), scratch_ptr or None, int(scratch_bytes),
+                                                cost_ptr or None, flow_ptr or None, status_ptr or None)
+        return rc == _native.RT_OK
+
+
+def path_scratch_bytes(origin, spacing, dims, clearance=0):
+    """rt_terrain_path_scratch_bytes: the bytes of path_field_device's scratch block for a lattice and a clearance
+    (0 for an invalid lattice or one without points)."""
+    lat = lattice(origin, spacing, dims)
+    opt = path_options(clearance=clearance)
+    return int(lib().rt_terrain_path_scratch_bytes(C.byref(lat), C.byref(opt)))
+
+
+def path_options(eye=None, clearance=0, max_cost=0, max_sweeps=0, max_blocks=0):
+    """An rt_path_options block: the eye of the terrain's own occupancy (None: the compute's Eye), the clearance in
+    cells, the largest cost that stays finite (0: unbounded), the sweeps (host form 0: until converged), the grids'
+    cap."""
+    opt = _native.RtPathOptions()
+    opt.size = C.sizeof(_native.RtPathOptions)
+    opt.flags = 0
+    if eye is not None:
+        opt.flags |= _native.RT_RAYS_EYE
+        opt.eye[:] = [float(x) for x in np.asarray(eye, np.float32).reshape(3)]
+    opt.max_blocks = int(max_blocks)
+    opt.clearance_cells = int(clearance)
+    opt.max_cost = int(max_cost)
+    opt.max_sweeps = int(max_sweeps)
+    return opt
+
+
+def seed_indices(seeds, dims):
+    """Flat uint32 point indices, (iz * ny + iy) * nx + ix, from (n, 3) ix, iy, iz rows or from flat indices."""
+    nx, ny, nz = (int(v) for v in dims)
+    s = np.asarray(seeds)
+    if s.ndim == 2 and s.shape[1] == 3:
+        s = s.astype(np.int64)
+        if s.size and ((s < 0).any() or (s >= np.array([nx, ny, nz])).any()):
+            raise ValueError("path_field: a seed is not a point of the lattice")
+        s = (s[:, 2] * ny + s[:, 1]) * nx + s[:, 0]
+    return np.ascontiguousarray(np.asarray(s).reshape(-1), np.uint32)
+
+
+_PATH_WEIGHT = (0, 3, 4, 5)
+
+
+def follow_flow(flow, start, max_len=None):
+    """The lattice points from `start` (ix, iy, iz) along a path field's flow to a seed, both ends included: a
+    (k, 3) int array of ix, iy, iz; empty from a point with no flow (RT_PATH_NONE).  Stops after max_len points
+    (None: the lattice's points, which no path exceeds).  Host code."""
+    flow = np.asarray(flow)
+    nz, ny, nx = flow.shape
+    x, y, z = (int(v) for v in start)
+    limit = flow.size if max_len is None else int(max_len)
+    out = []
+    while len(out) < limit:
+        c = int(flow[z, y, x])
+        if c == _native.RT_PATH_NONE:
+            return np.zeros((0, 3), np.int64) if not out else np.array(out, np.int64)
+        out.append((x, y, z))
+        if c == 13:
+            break
+        x, y, z = x + c % 3 - 1, y + c // 3 % 3 - 1, z + c // 9 - 1
+        if not (0 <= x < nx and 0 <= y < ny and 0 <= z < nz):
+            break
+    return np.array(out, np.int64).reshape(-1, 3)
+
+
+def path_cost_along(points):
+    """The summed 3-4-5 weights of the moves between consecutive points of a (k, 3) lattice path."""
+    p = np.asarray(points, np.int64).reshape(-1, 3)
+    steps = (np.diff(p, axis=0) != 0).sum(axis=1)
+    return int(sum(_PATH_WEIGHT[int(k)] for k in steps))
+
 
 def distance_scratch_bytes(origin, spacing, dims):
     """rt_terrain_distance_scratch_bytes: the bytes of distance_field_device's scratch block for a lattice (0 for an

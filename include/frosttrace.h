@@ -784,6 +784,83 @@ int rt_terrain_distance_field_device(rt_compute cs, const rt_lattice* lat, const
                                      const void* occupancy_in_device, void* scratch_device, size_t scratch_bytes,
                                      void* d2_device, void* distance_device);
 
+/* ---- path fields (ABI 9, additive; no reference counterpart) ----
+ * The step from "where may I stand" to "how do I get there": for every point of a lattice the cost of the cheapest
+ * path from a set of seed points through the passable points, and optionally the move that starts that path back
+ * to a seed (a flow field, what a crowd steers by).  Formed on the device from the occupancy bits; a clearance uses
+ * the distance passes above.  The answer is unique: it is the least fixed point of an integer relaxation, so the
+ * kernels may relax in any order and still equal a Dijkstra search bit for bit.
+ * The lattice is an rt_lattice exactly as rt_terrain_sample_lattice reads it; point index and occupancy word layout
+ *   as there.
+ * Blocked and passable.  A point is BLOCKED when its occupancy bit is set.
+ *   occupancy_in NULL: the terrain's own occupancy, computed on the device into the scratch block as the distance
+ *     field does it (RT_RAYS_EYE and max_blocks as there, either kind of compute).
+ *   occupancy_in not NULL: the caller's words; the terrain is not evaluated.  The padding bits of a row's last word
+ *     are ignored whatever they hold.
+ *   clearance_cells = R > 0: a point is PASSABLE iff it is not blocked and its d2 is greater than R * R, d2 exactly
+ *     rt_terrain_distance_field's (the squared distance of an outside point to the nearest blocked point; far when
+ *     the lattice has none).  R == 0: passable iff not blocked.
+ * Moves.  The 26 neighbours.  Move code c = (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1), 0..26, 13 is "stay".  Weight w(c)
+ *   is 3 for a face move, 4 for an edge move, 5 for a corner move: the 3-4-5 chamfer, in thirds of a cell.  A move is
+ *   allowed when both of its ends are passable lattice points.
+ * Seeds.  seeds[0 .. n_seeds) are linear point indices, (iz * ny + iy) * nx + ix.  Duplicates are allowed.  A seed
+ *   that is blocked or impassable contributes nothing.  A seed at or beyond nx * ny * nz is RT_ERR_INVALID in the
+ *   host form; the device form cannot check, so its kernel skips such a seed.
+ * Cost.
+ *     cost(p) = min over seeds s and move sequences from s to p of the sum of w      uint32, exact
+ *             = 0 at a passable seed
+ *             = RT_PATH_FAR where p is impassable, unreachable, or, with max_cost = M > 0, where that minimum
+ *               exceeds M
+ *   max_cost bounds the work as well as the answer: a candidate above M is never stored or propagated.  That is
+ *   still exact, because every prefix of a cheapest path is cheaper than the whole path.  The largest finite cost is
+ *   below 5 * 2^26 (a path visits a point once, and a lattice has 2^26 points at most), and the far value is never
+ *   added to, so no sum overflows.
+ * Flow (optional, uint8 a point).  The smallest move code c for which the neighbour q = p + move(c) has
+ *   cost(q) + w(c) == cost(p): the first step of a cheapest path back to a seed.  13 at a point of cost 0,
+ *   RT_PATH_NONE where the cost is far.  The flow is determined by cost alone.  (In an unconverged field a point
+ *   whose neighbours have fallen since it was written may have no such c: RT_PATH_NONE.)
+ * World length.  cost * |spacing| / 3 on an isotropic lattice.  In open space the chamfer length of the offset
+ *   (a, b, c), a >= b >= c >= 0, is a + (b + c) / 3; against the Euclidean sqrt(a^2 + b^2 + c^2) it lies between
+ *   -5.7% (at (1, 1, 0): 4/3 for sqrt 2) and +10.6% (at (1, 1/3, 1/3): 11/9 for sqrt(11)/3).
+ * Status (4 uint32): [0] 1 when the relaxation converged, else 0; [1] sweeps that did work; [2] points with a
+ *   finite cost; [3] 0.  When [0] == 0 every written cost is an upper bound of the true cost (the cost of a real
+ *   path), and the cost of a passable seed is 0.
+ * opt (NULL: the defaults) is an rt_path_options: size >= 36, flags RT_RAYS_EYE or 0, eye, max_blocks (the cap of
+ *   every pass's grid, 0: none), clearance_cells (<= 4095), max_cost (0: unbounded), max_sweeps.
+ * cost is required; flow may be NULL; status may be NULL in the host form and is required in the device form.
+ *   n_seeds is 1 .. 2^26.
+ * rt_terrain_path_scratch_bytes: the device form's scratch block for the lattice and opt->clearance_cells: the
+ *   occupancy words; with a clearance the distance scratch and a word a point for d2; the passable words; two tile
+ *   flag arrays (a word a tile of 32 x 4 x 4 points each); 64 bytes of counters; each part rounded up to 16 bytes.
+ *   0 for an invalid lattice or option block, or a lattice without points.
+ * rt_terrain_path_field: host arrays; blocking.  max_sweeps == 0 sweeps until converged; that ends, because every
+ *   working sweep lowers at least one non-negative integer.  A positive max_sweeps stops there and returns RT_OK
+ *   with status[0] == 0 if the field has not converged.  Nothing but the arrays asked for is downloaded.
+ * rt_terrain_path_field_device: device arrays (4-byte aligned but flow), enqueued on the compute's device stream; it
+ *   allocates nothing and never synchronises the host.  max_sweeps must be 1..4096: it enqueues an initialisation,
+ *   exactly that many sweep launches and a finish pass; a sweep launch that finds nothing active ends at once.
+ *   With H the greatest number of moves on any cheapest path, max_sweeps >= H + 2 converges; every move costs at
+ *   least 3, so H <= (largest finite cost) / 3.
+ * Both: RT_ERR_INVALID for the lattice's errors (as rt_terrain_sample_lattice), a NULL compute or lattice,
+ *   opt->size < 36, flags other than RT_RAYS_EYE, clearance_cells > 4095, n_seeds outside 1..2^26, NULL seeds or
+ *   cost, and in the device form a NULL status, max_sweeps outside 1..4096 or a scratch block that is NULL or below
+ *   rt_terrain_path_scratch_bytes; nothing is written then.  RT_ERR_STATE as for the distance field (texPerm2D bound
+ *   and the fail-safe word clear, with a given occupancy too).  A dims product of 0 is RT_OK and launches nothing.
+ *   Like every query it reads no frame state and changes none.
+ * Out of scope: continuing an unconverged field; per-seed start costs and per-cell traversal weights; a rule
+ *   against diagonal moves between two blocked cells (a clearance of one cell or more is the remedy);
+ *   walkable-surface (gravity) navigation; sub-cell paths, any-angle smoothing, anisotropic weights, an eye per
+ *   point. */
+#define RT_PATH_FAR 0xFFFFFFFFu
+#define RT_PATH_NONE 255u
+typedef struct { uint32_t size, flags; float eye[3]; uint32_t max_blocks, clearance_cells, max_cost, max_sweeps; } rt_path_options; /* 36 bytes, v1 */
+size_t rt_terrain_path_scratch_bytes(const rt_lattice* lat, const rt_path_options* opt);
+int rt_terrain_path_field(rt_compute cs, const rt_lattice* lat, const rt_path_options* opt, const uint32_t* occupancy_in,
+                          const uint32_t* seeds, uint32_t n_seeds, uint32_t* cost, uint8_t* flow, uint32_t status[4]);
+int rt_terrain_path_field_device(rt_compute cs, const rt_lattice* lat, const rt_path_options* opt, const void* occupancy_in_device,
+                                 const void* seeds_device, uint32_t n_seeds, void* scratch_device, size_t scratch_bytes,
+                                 void* cost_device, void* flow_device, void* status_device);
+
 /* ---- diagnostics (primitive-level parity tests; no reference counterpart) ----
  * rt_debug_math: device evaluation of the numeric primitives of DESIGN.md §Numerics
  *   (op 0 exp2, 1 log2, 2 exp, 3 sin, 4 cos, 5 sqrt, 6 rcp, 7 rsqrt, 8 pow, 9 max,
