@@ -92,6 +92,15 @@ class RtPathOptions(C.Structure):
                 ("clearance_cells", C.c_uint32), ("max_cost", C.c_uint32), ("max_sweeps", C.c_uint32)]
 
 
+RT_VIS_POINT = 0  # an observer's kind: the lattice point (x, y, z)
+RT_VIS_DIRECTION = 1  # the integer direction (x, y, z) towards the light
+
+
+class RtVisibilityOptions(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("eye", C.c_float * 3), ("max_blocks", C.c_uint32),
+                ("max_range", C.c_uint32)]
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -203,6 +212,13 @@ SIGNATURES = {
                                    _vp]),
     "rt_terrain_path_field_device": (_i, [_vp, C.POINTER(RtLattice), C.POINTER(RtPathOptions), _vp, _vp, C.c_uint32,
                                           _vp, _sz, _vp, _vp, _vp]),
+    # visibility fields: for every point of a lattice the mask (uint32) of the observers (x, y, z, kind int32 records)
+    # it has a free line of sight to over the occupancy bits, and four status words; the device form takes its scratch
+    "rt_terrain_visibility_scratch_bytes": (_sz, [C.POINTER(RtLattice)]),
+    "rt_terrain_visibility_field": (_i, [_vp, C.POINTER(RtLattice), C.POINTER(RtVisibilityOptions), _vp, _vp, C.c_uint32,
+                                         _vp, _vp]),
+    "rt_terrain_visibility_field_device": (_i, [_vp, C.POINTER(RtLattice), C.POINTER(RtVisibilityOptions), _vp, _vp,
+                                                C.c_uint32, _vp, _sz, _vp, _vp]),
     "rt_noise_generate": (_i, [C.c_uint32, _i, _vp, _vp]),
     "rt_terrain_set_target_depths": (_i, [_vp, _vp]),
     "rt_recorder_create": (_i, [_vp, _i, _i, _cp, C.POINTER(_vp)]),

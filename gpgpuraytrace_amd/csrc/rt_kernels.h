@@ -294,6 +294,24 @@ struct RtPathQuery {
 };
 bool rt_launch_pathquery(const RtLaunch& a, const RtPathQuery& q);
 
+// A visibility field's one pass (rt_terrain_visibility_field; the definition is in include/frosttrace.h, the walk and
+// the scratch layout in rt_rayquery.h): k_visibility stores for every point the mask of the observers it sees.
+// `occupancy` as in RtDistanceQuery; `observers`: n_observers (1..rtq::kVisMaxObservers) records x, y, z, kind, an
+// invalid one seeing nothing; range2: max_range squared, 0 for none.  counters (may be null: nothing is counted):
+// four words that are 0 when the kernel starts, zeroed on a.stream by the caller, and hold the status after it.
+// All dims >= 1 with a product of 2^26 at most; blocks of rtq::kDistThreads threads.  false: nothing launched.
+struct RtVisibilityQuery {
+    const uint32_t* occupancy;
+    const int32_t* observers;
+    uint32_t n_observers;
+    uint32_t dims[3];
+    uint32_t range2;
+    uint32_t* mask;
+    uint32_t* counters;
+    uint32_t blocks;
+};
+bool rt_launch_visibilityquery(const RtLaunch& a, const RtVisibilityQuery& q);
+
 #define RT_TILE 32
 #define RT_FIN_SLOTS 1536 // k_trace's fin pool slots per block
 #define RT_AO_POOL_SLOTS 256 // k_trace's AO counter slots per block (LDS) and their colours (cpool)

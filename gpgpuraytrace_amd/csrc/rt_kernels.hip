@@ -3657,6 +3657,70 @@ bool rt_launch_pathquery(const RtLaunch& a, const RtPathQuery& q)
 }
 
 // ---------------------------------------------------------------------------
+// Visibility fields (rt_terrain_visibility_field): for every point the mask of the observers it has a free line of
+// sight to, from the occupancy words alone (include/frosttrace.h has the definition, rt_rayquery.h the walk,
+// rtq::vis_sees, and the scratch layout).  A thread a point in result order, the observers in a loop inside it: the
+// observer record is the same in every lane, a wave's 64 points are consecutive ix of a row (or of the rows that
+// follow), so its lanes walk near-parallel lines and mostly read the same occupancy word; the mask is put together
+// in a register and stored once.  No LDS, no workgroup waits on another; every walk is bounded by the dims' sum.
+namespace {
+
+struct VisParams {
+    uint32_t nx, ny, nz, points;
+    uint32_t range2; // max_range squared, 0: none
+    uint32_t n_observers;
+};
+
+__global__ void __launch_bounds__(rtq::kDistThreads) k_visibility(const uint32_t* __restrict__ occ, const int32_t* __restrict__ observers,
+                                                                 uint32_t* __restrict__ mask, uint32_t* counters, VisParams p)
+{
+    const uint32_t dims[3] = {p.nx, p.ny, p.nz};
+    const rtq::VisGrid g = rtq::vis_grid(dims);
+    uint32_t seeing = 0u, bits = 0u;
+    for (uint32_t i = blockIdx.x * rtq::kDistThreads + threadIdx.x; i < p.points; i += gridDim.x * rtq::kDistThreads) {
+        const uint32_t row = i / p.nx, ix = i - row * p.nx, iz = row / p.ny, iy = row - iz * p.ny;
+        uint32_t m = 0u;
+        for (uint32_t k = 0; k < p.n_observers; ++k) {
+            const int32_t o[4] = {observers[4u * k], observers[4u * k + 1u], observers[4u * k + 2u], observers[4u * k + 3u]};
+            if (!rtq::vis_observer_valid(o, dims)) continue; // (the same in every lane) it sees nothing
+            if (rtq::vis_sees([&](uint32_t bit) { return rtq::vis_bit(occ, bit); }, g, ix, iy, iz, o, p.range2)) m |= 1u << k;
+        }
+        mask[i] = m;
+        seeing += m != 0u;
+        bits += (uint32_t)__popc(m);
+    }
+    if (!counters) return;
+    // the status: a reduction in the wave, then two atomics a wave
+    for (int off = 32; off > 0; off >>= 1) {
+        seeing += __shfl_down(seeing, off, 64);
+        bits += __shfl_down(bits, off, 64);
+    }
+    if ((threadIdx.x & 63u) == 0u && bits) {
+        atomicAdd(counters + 0, seeing);
+        atomicAdd(counters + 1, bits);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        uint32_t valid = 0u;
+        for (uint32_t k = 0; k < p.n_observers; ++k) valid += rtq::vis_observer_valid(observers + 4u * k, dims);
+        counters[2] = valid;
+    }
+}
+
+} // namespace
+
+bool rt_launch_visibilityquery(const RtLaunch& a, const RtVisibilityQuery& q)
+{
+    const uint64_t points = (uint64_t)q.dims[0] * q.dims[1] * q.dims[2];
+    if (points == 0 || points > (1u << 26) || q.blocks == 0) return false;
+    if (q.dims[0] > rtq::kMaxLatticeDim || q.dims[1] > rtq::kMaxLatticeDim || q.dims[2] > rtq::kMaxLatticeDim) return false;
+    if (!q.occupancy || !q.observers || !q.mask || q.n_observers == 0 || q.n_observers > rtq::kVisMaxObservers) return false;
+    const VisParams p{q.dims[0], q.dims[1], q.dims[2], (uint32_t)points, q.range2, q.n_observers};
+    hipLaunchKernelGGL(k_visibility, dim3(q.blocks), dim3(rtq::kDistThreads), 0, a.stream, q.occupancy, q.observers, q.mask,
+                       q.counters, p);
+    return true;
+}
+
+// ---------------------------------------------------------------------------
 // Diagnostics: device evaluation of the numeric primitives, noise3d and
 // getDensity for the primitive-level parity tests (tests/test_gpu_parity.py).
 namespace {

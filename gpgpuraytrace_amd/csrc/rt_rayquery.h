@@ -5,7 +5,7 @@
 // grids and mask arithmetic of rt_terrain_extract_mesh.  No HIP in here (the mask arithmetic is marked
 // __host__ __device__ under hipcc only, for k_meshcount): tests/tools/rayquery_check.cpp, surfquery_check.cpp,
 // shadequery_check.cpp, pointquery_check.cpp, fieldquery_check.cpp, meshquery_check.cpp, distquery_check.cpp,
-// pathquery_check.cpp and querylayout_check.cpp
+// pathquery_check.cpp, visquery_check.cpp and querylayout_check.cpp
 // drive it stand-alone under ASan + UBSan.
 #pragma once
 
@@ -854,6 +854,174 @@ inline PathPlan plan_path(const PathScratch& s, uint32_t max_blocks, int cus)
     PathPlan p;
     p.sweep_blocks = field_grid(s.tiles.total, max_blocks, 4 * (cus > 0 ? cus : 1));
     p.point_blocks = plan_distance(s.points, max_blocks, cus).blocks;
+    return p;
+}
+
+// ---- visibility fields (rt_terrain_visibility_field): line of sight to observers on the occupancy bits ----
+//
+// One kernel, k_visibility, a thread a point: for each observer the walk of include/frosttrace.h from the point
+// towards the observer (the rule is symmetric) or along the direction, over the occupancy words alone.  The walk
+// is VisWalk and vis_sees below, host and device, so tests/tools/visquery_check.cpp runs the code the kernel runs.
+
+// the first version of rt_visibility_options: size, flags, eye[3], max_blocks, max_range
+constexpr uint32_t kVisOptSizeV1 = 28u;
+constexpr uint32_t kVisMaxObservers = 32u;
+constexpr int32_t kVisMaxDirection = 4095;               // of a direction's components, in magnitude
+constexpr uint32_t kVisMaxRange = 2u * (kMaxLatticeDim - 1u); // no two lattice points are farther apart
+enum { VIS_POINT = 0, VIS_DIRECTION = 1 };                // an observer's kind
+
+struct VisibilityOptions : Options {
+    uint32_t max_range = 0; // 0: unbounded
+};
+
+// `opt` is the caller's rt_visibility_options (may be null: the defaults), read as far as the first version reaches.
+inline int parse_visibility_options(const void* opt, VisibilityOptions* out, const char** why)
+{
+    *out = VisibilityOptions{};
+    if (!opt) return OK;
+    if (!parse_prefix(opt, kVisOptSizeV1, out)) {
+        *why = "rt_visibility_options.size is smaller than the struct's first version";
+        return INVALID;
+    }
+    if (out->flags & ~kEye) {
+        *why = "rt_visibility_options.flags has bits other than RT_RAYS_EYE";
+        return INVALID;
+    }
+    std::memcpy(&out->max_range, static_cast<const char*>(opt) + 24, 4);
+    if (out->max_range > kVisMaxRange) {
+        *why = "rt_visibility_options.max_range is above 8190";
+        return INVALID;
+    }
+    return OK;
+}
+
+// an observer record x, y, z, kind that the definition admits on a lattice of these dims
+RTQ_HD inline bool vis_observer_valid(const int32_t o[4], const uint32_t dims[3])
+{
+    if (o[3] == VIS_POINT) // (a negative coordinate wraps: >= dim)
+        return (uint32_t)o[0] < dims[0] && (uint32_t)o[1] < dims[1] && (uint32_t)o[2] < dims[2];
+    if (o[3] != VIS_DIRECTION) return false;
+    for (int i = 0; i < 3; ++i)
+        if (o[i] > kVisMaxDirection || o[i] < -kVisMaxDirection) return false;
+    return (o[0] | o[1] | o[2]) != 0;
+}
+
+// The crossing events of a walk whose axis i crosses a boundary at t = (2 k + 1) / (2 n[i]), k = 0, 1, ...
+// (n[i] = |d_i| or |u_i|, 4095 at most; 0: the axis never crosses).  With a_i = 2 k_i + 1 the next crossing of axis
+// i, t_i <= t_j is a_i n[j] <= a_j n[i]: the walk holds the three differences a_i n[j] - a_j n[i] and moves them by
+// additions when an axis steps, so an event costs no multiply.  An axis with n[i] == 0 compares later than every
+// axis that crosses (its difference keeps the sign of a n[j] > 0), and so does an axis that has taken all n[i] steps
+// of a point walk (its t is above 1), so neither needs a case of its own.  While no axis has taken more than 4096
+// steps every difference is below 8193 * 4095 < 2^25 in magnitude.
+struct VisWalk {
+    int32_t n[3];
+    int32_t dxy, dxz, dyz;
+    RTQ_HD void start(int32_t nx, int32_t ny, int32_t nz)
+    {
+        n[0] = nx, n[1] = ny, n[2] = nz;
+        dxy = ny - nx, dxz = nz - nx, dyz = nz - ny;
+    }
+    // the next event: the axes that cross at the earliest time, x 1, y 2, z 4 (one at least while an n is not 0)
+    RTQ_HD uint32_t step()
+    {
+        const bool sx = dxy <= 0 && dxz <= 0, sy = dxy >= 0 && dyz <= 0, sz = dxz >= 0 && dyz >= 0;
+        if (sx) dxy += 2 * n[1], dxz += 2 * n[2];
+        if (sy) dxy -= 2 * n[0], dyz += 2 * n[2];
+        if (sz) dxz -= 2 * n[0], dyz -= 2 * n[1];
+        return (uint32_t)sx | (uint32_t)sy << 1 | (uint32_t)sz << 2;
+    }
+};
+
+// The occupancy words as one run of bits: point (ix, iy, iz) is bit (iz ny + iy) row_bits + ix, word bit >> 5, bit
+// bit & 31 of it; below 2^31 for a lattice of 2^26 points.  A step along x, y, z moves it by 1, row_bits, plane_bits.
+struct VisGrid {
+    uint32_t nx, ny, nz;
+    uint32_t row_bits, plane_bits;
+};
+RTQ_HD inline VisGrid vis_grid(const uint32_t dims[3])
+{
+    VisGrid g;
+    g.nx = dims[0], g.ny = dims[1], g.nz = dims[2];
+    g.row_bits = (dims[0] + 31u) / 32u * 32u;
+    g.plane_bits = g.row_bits * dims[1];
+    return g;
+}
+
+// Whether the lattice point p = (ix, iy, iz) sees the valid observer o (vis_observer_valid).  blocked(bit): the
+// occupancy bit of the point at that bit index; it is asked for cells of the lattice between the ends only, never
+// for p or a point observer.  range2: max_range^2, 0 for none.  The walk starts at p.  A point walk ends at o after
+// |d_x| + |d_y| + |d_z| axis steps, a directional walk where it leaves the lattice, so the loop runs nx + ny + nz
+// times at most.
+template <class Blocked>
+RTQ_HD inline bool vis_sees(Blocked blocked, const VisGrid& g, uint32_t ix, uint32_t iy, uint32_t iz, const int32_t o[4],
+                            uint32_t range2)
+{
+    const bool directional = o[3] == VIS_DIRECTION;
+    const int32_t dx = directional ? o[0] : o[0] - (int32_t)ix, dy = directional ? o[1] : o[1] - (int32_t)iy,
+                  dz = directional ? o[2] : o[2] - (int32_t)iz;
+    const int32_t nx = dx < 0 ? -dx : dx, ny = dy < 0 ? -dy : dy, nz = dz < 0 ? -dz : dz;
+    int32_t left = 0x7fffffff; // axis steps to the observer; a direction has no end
+    if (!directional) {
+        if (range2 && (uint32_t)(dx * dx + dy * dy + dz * dz) > range2) return false;
+        left = nx + ny + nz;
+        if (left == 0) return true;
+    }
+    // (a step below 0 wraps, and a negative bit step is its two's complement)
+    const uint32_t sx = dx < 0 ? ~0u : 1u, sy = dy < 0 ? ~0u : 1u, sz = dz < 0 ? ~0u : 1u;
+    const uint32_t bx = sx, by = dy < 0 ? 0u - g.row_bits : g.row_bits, bz = dz < 0 ? 0u - g.plane_bits : g.plane_bits;
+    uint32_t x = ix, y = iy, z = iz, bit = (iz * g.ny + iy) * g.row_bits + ix;
+    VisWalk w;
+    w.start(nx, ny, nz);
+    for (;;) {
+        const uint32_t axes = w.step();
+        if (axes & 1u) x += sx, bit += bx;
+        if (axes & 2u) y += sy, bit += by;
+        if (axes & 4u) z += sz, bit += bz;
+        if (x >= g.nx || y >= g.ny || z >= g.nz) return true; // left the lattice unblocked (a point walk never does)
+        if (!directional) {
+            left -= (int32_t)((axes & 1u) + (axes >> 1 & 1u) + (axes >> 2));
+            if (left <= 0) return true; // at the observer, which is not tested
+        } else if (range2) {
+            const int32_t ex = (int32_t)(x - ix), ey = (int32_t)(y - iy), ez = (int32_t)(z - iz);
+            if ((uint32_t)(ex * ex + ey * ey + ez * ez) > range2) return true;
+        }
+        if (blocked(bit)) return false;
+    }
+}
+
+// the occupancy bit at a bit index of vis_grid's numbering
+RTQ_HD inline bool vis_bit(const uint32_t* occupancy, uint32_t bit) { return (occupancy[bit >> 5] >> (bit & 31u)) & 1u; }
+
+// The scratch block of a visibility field, laid out by block_layout: the lattice's occupancy words (used when the
+// terrain's own occupancy is asked for) and the counters, VIS_CNT_WORDS uint32, of which the first four are the
+// host form's status words.
+constexpr uint32_t VIS_CNT_WORDS = 16u;
+struct VisibilityScratch {
+    uint32_t points = 0; // nx ny nz
+    BlockLayout lay;     // parts: occupancy, counters; total 0 without points
+};
+enum { VIS_OCCUPANCY = 0, VIS_COUNTERS = 1 };
+
+// dims of a lattice that check_lattice passed
+inline VisibilityScratch visibility_scratch(const uint32_t dims[3])
+{
+    VisibilityScratch s;
+    s.points = dims[0] * dims[1] * dims[2];
+    if (s.points == 0) return s;
+    const size_t bytes[2] = {occupancy_bytes(dims), (size_t)VIS_CNT_WORDS * 4};
+    s.lay = block_layout(bytes, 2);
+    return s;
+}
+
+// The grid: a thread a point in blocks of kDistThreads threads striding over the points, as the distance passes;
+// no LDS, eight blocks a CU resident.
+struct VisibilityPlan {
+    uint32_t blocks = 0;
+};
+inline VisibilityPlan plan_visibility(uint32_t points, uint32_t max_blocks, int cus)
+{
+    VisibilityPlan p;
+    p.blocks = plan_distance(points, max_blocks, cus).blocks;
     return p;
 }
 

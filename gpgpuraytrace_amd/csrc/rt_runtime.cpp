@@ -3790,6 +3790,121 @@ extern "C" int rt_terrain_path_field_device(rt_compute c, const rt_lattice* lat,
 }
 
 // ---------------------------------------------------------------------------
+// rt_terrain_visibility_field: for every point the observers it has a free line of sight to (include/frosttrace.h):
+// the caller's occupancy words, or the lattice query's occupancy pass into the scratch block, then the one
+// visibility pass (rt_launch_visibilityquery), all on the device stream.
+namespace {
+
+// enqueue one visibility field (no host synchronisation, no allocation); the scratch block holds s.lay.total bytes;
+// occupancy null: the terrain's own; counters null: nothing is counted
+int visibility_field_enqueue(rt_compute c, const rtq::Lattice& l, const rtq::VisibilityScratch& s,
+                             const rtq::VisibilityOptions& o, const void* occupancy, const void* observers,
+                             uint32_t n_observers, char* scratch, void* mask, void* counters)
+{
+    rt_device dev = c->dev;
+    if (!occupancy) {
+        rtq::FieldOptions occ_opt = o; // the eye and the grid's cap
+        void* own = scratch + s.lay.offset[rtq::VIS_OCCUPANCY];
+        if (int rc = sample_field_enqueue(c, nullptr, &l, s.points, occ_opt, nullptr, own)) return rc;
+        occupancy = own;
+    }
+    // the counts start from 0: zeroed on the stream the kernel runs on, so the two are ordered
+    if (counters) HIP_TRY(hipMemsetAsync(counters, 0, 16, dev->stream));
+    const RtLaunch a = make_launch(dev, c->shader);
+    RtVisibilityQuery q{};
+    q.occupancy = (const uint32_t*)occupancy;
+    q.observers = (const int32_t*)observers;
+    q.n_observers = n_observers;
+    memcpy(q.dims, l.dims, sizeof(q.dims));
+    q.range2 = o.max_range * o.max_range;
+    q.mask = (uint32_t*)mask;
+    q.counters = (uint32_t*)counters;
+    q.blocks = rtq::plan_visibility(s.points, o.max_blocks, cus_of(dev)).blocks;
+    return query_launched(rt_launch_visibilityquery(a, q), "rt_terrain_visibility_field: no kernel for this query");
+}
+
+// both entry points; host: the blocking form, whose arrays are the host's
+int visibility_field_entry(const char* who, rt_compute c, const rt_lattice* lat, const rt_visibility_options* opt,
+                           const void* occupancy, const void* observers, uint32_t n_observers, void* scratch,
+                           size_t scratch_bytes, void* mask, void* status, bool host)
+{
+    const QueryFamily<rtq::VisibilityOptions> f{who, nullptr, rtq::parse_visibility_options};
+    rtq::Lattice l;
+    rtq::VisibilityScratch s;
+    std::string missing = std::string(who) + ": observers or mask is null";
+    return query_entry(
+        c, f, 0, opt,
+        [&](const rtq::VisibilityOptions&, uint32_t* n) -> int {
+            const char* why = "";
+            if (int rc = rtq::check_lattice(lat, &l, n, &why)) return fail(rc, "%s: %s", who, why);
+            s = rtq::visibility_scratch(l.dims);
+            if (n_observers < 1u || n_observers > rtq::kVisMaxObservers)
+                return fail(RT_ERR_INVALID, "%s: n_observers must be 1..32", who);
+            if (host && observers && *n) {
+                const int32_t* ob = (const int32_t*)observers;
+                for (uint32_t i = 0; i < n_observers; ++i)
+                    if (!rtq::vis_observer_valid(ob + 4 * (size_t)i, l.dims))
+                        return fail(RT_ERR_INVALID,
+                                    "%s: observer %u is no point of the lattice, no direction of components within +-4095 "
+                                    "that are not all 0, or of an unknown kind",
+                                    who, i);
+            }
+            if (!host && *n) {
+                if (!scratch || scratch_bytes < s.lay.total)
+                    return fail(RT_ERR_INVALID, "%s: the scratch block is null or below rt_terrain_visibility_scratch_bytes", who);
+                if (((uintptr_t)scratch | (uintptr_t)occupancy | (uintptr_t)observers | (uintptr_t)mask | (uintptr_t)status) % 4)
+                    return fail(RT_ERR_INVALID, "%s: the device arrays must be 4-byte aligned", who);
+            }
+            return RT_OK;
+        },
+        !observers || !mask ? missing.c_str() : nullptr,
+        [&](const rtq::VisibilityOptions& o, uint32_t n) -> int {
+            if (!host)
+                return visibility_field_enqueue(c, l, s, o, occupancy, observers, n_observers, (char*)scratch, mask, status);
+            // one device block: the scratch (its counters the status words), the caller's occupancy words, the
+            // observers, the result
+            const HostPart parts[] = {{s.lay.total, nullptr, nullptr},
+                                      {occupancy ? rtq::occupancy_bytes(l.dims) : 0, occupancy, nullptr},
+                                      {(size_t)n_observers * 16, observers, nullptr},
+                                      {(size_t)n * 4, nullptr, mask}};
+            return host_form(c->dev, parts, [&](char* const* at) -> int {
+                char* counters = status ? at[0] + s.lay.offset[rtq::VIS_COUNTERS] : nullptr;
+                if (int rc = visibility_field_enqueue(c, l, s, o, at[1], at[2], n_observers, at[0], at[3], counters)) return rc;
+                if (status) HIP_TRY(hipMemcpyAsync(status, counters, 16, hipMemcpyDeviceToHost, c->dev->stream));
+                return RT_OK;
+            });
+        });
+}
+
+} // namespace
+
+extern "C" size_t rt_terrain_visibility_scratch_bytes(const rt_lattice* lat)
+{
+    rtq::Lattice l;
+    uint32_t n = 0;
+    const char* why = "";
+    if (rtq::check_lattice(lat, &l, &n, &why)) return 0;
+    return rtq::visibility_scratch(l.dims).lay.total;
+}
+
+extern "C" int rt_terrain_visibility_field(rt_compute c, const rt_lattice* lat, const rt_visibility_options* opt,
+                                           const uint32_t* occupancy_in, const int32_t* observers, uint32_t n_observers,
+                                           uint32_t* mask, uint32_t status[4])
+{
+    return visibility_field_entry("rt_terrain_visibility_field", c, lat, opt, occupancy_in, observers, n_observers, nullptr, 0,
+                                  mask, status, true);
+}
+
+extern "C" int rt_terrain_visibility_field_device(rt_compute c, const rt_lattice* lat, const rt_visibility_options* opt,
+                                                  const void* occupancy_in_device, const void* observers_device,
+                                                  uint32_t n_observers, void* scratch_device, size_t scratch_bytes,
+                                                  void* mask_device, void* status_device)
+{
+    return visibility_field_entry("rt_terrain_visibility_field_device", c, lat, opt, occupancy_in_device, observers_device,
+                                  n_observers, scratch_device, scratch_bytes, mask_device, status_device, false);
+}
+
+// ---------------------------------------------------------------------------
 // rt_readback_*: the asynchronous readback ring (struct rt_readback_s above; include/frosttrace.h)
 int rt_readback_create(rt_device d, int format, int depth, rt_readback* out)
 {

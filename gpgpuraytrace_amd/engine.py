@@ -995,6 +995,133 @@ class Terrain:
                                                 cost_ptr or None, flow_ptr or None, status_ptr or None)
         return rc == _native.RT_OK
 
+    def visibility_field(self, origin, spacing, dims, observers=None, directions=None, eye=None, max_range=0,
+                         occupancy=None, max_blocks=0, status=None):
+        """rt_terrain_visibility_field: for every point of the lattice (sample_lattice's origin, spacing and dims) the
+        observers it has a free line of sight to over the occupancy bits, an array shaped (nz, ny, nx) uint32: bit k
+        is set where the point sees observer k.  observers: (n, 3) ix, iy, iz lattice points, which take the low
+        bits in order; directions: (m, 3) integer directions towards a light (lattice_direction), which take the
+        next bits, set where the point is lit; n + m is 1..32.  The ends of a line are not tested, so a blocked
+        surface point that is met first is seen.  max_range: in cells, 0 for unbounded; a point observer farther
+        away is not seen, a shadow caster farther away does not count.  occupancy: None for the terrain's own, or
+        bit words as sample_lattice returns them.  status: a list that receives the four status words (points with
+        a bit set, bits set, valid observers, 0).  None if the call fails.  Blocking; uses the camerarays compute."""
+        lat, (nx, ny, nz) = lattice(origin, spacing, dims), (int(v) for v in dims)
+        opt = visibility_options(eye, max_range, max_blocks)
+        occ = None
+        if occupancy is not None:
+            occ = np.ascontiguousarray(occupancy, np.uint32)
+            if occ.size != nz * ny * ((nx + 31) // 32):
+                raise ValueError("visibility_field: occupancy must hold ceil(nx / 32) * ny * nz words")
+        ob = pack_observers(observers, directions, (nx, ny, nz))
+        self.update_shaders()
+        mask = np.empty((nz, ny, nx), np.uint32)
+        st = np.zeros(4, np.uint32)
+        rc = lib().rt_terrain_visibility_field(self.camera_compute._h, C.byref(lat), C.byref(opt),
+                                               occ.ctypes.data if occ is not None and occ.size else None,
+                                               ob.ctypes.data, int(ob.shape[0]), mask.ctypes.data, st.ctypes.data)
+        if rc != _native.RT_OK:
+            return None
+        if status is not None:
+            status[:] = [int(v) for v in st]
+        return mask
+
+    def visibility_field_device(self, origin, spacing, dims, observers_ptr, n_observers, scratch_ptr, scratch_bytes,
+                                mask_ptr, status_ptr=0, occupancy_ptr=0, eye=None, max_range=0, max_blocks=0):
+        """rt_terrain_visibility_field_device: the same into device arrays -- observers_ptr n_observers records of
+        four int32 (pack_observers), scratch_ptr at least visibility_scratch_bytes(origin, spacing, dims) bytes,
+        mask_ptr nx ny nz uint32, status_ptr 4 uint32 or 0, occupancy_ptr the caller's bit words or 0 for the
+        terrain's own -- enqueued on the device's stream with no host synchronisation and no allocation.  An invalid
+        observer record sees nothing.  True on success."""
+        lat = lattice(origin, spacing, dims)
+        opt = visibility_options(eye, max_range, max_blocks)
+        self.update_shaders()
+        rc = lib().rt_terrain_visibility_field_device(self.camera_compute._h, C.byref(lat), C.byref(opt),
+                                                      occupancy_ptr or None, observers_ptr or None, int(n_observers),
+                                                      scratch_ptr or None, int(scratch_bytes), mask_ptr or None,
+                                                      status_ptr or None)
+        return rc == _native.RT_OK
+
+
+def visibility_scratch_bytes(origin, spacing, dims):
+    """rt_terrain_visibility_scratch_bytes: the bytes of visibility_field_device's scratch block for a lattice (0 for
+    an invalid lattice or one without points)."""
+    lat = lattice(origin, spacing, dims)
+    return int(lib().rt_terrain_visibility_scratch_bytes(C.byref(lat)))
+
+
+def visibility_options(eye=None, max_range=0, max_blocks=0):
+    """An rt_visibility_options block: the eye of the terrain's own occupancy (None: the compute's Eye), the range in
+    cells (0: unbounded, 8190 at most), the grid's cap."""
+    opt = _native.RtVisibilityOptions()
+    opt.size = C.sizeof(_native.RtVisibilityOptions)
+    opt.flags = 0
+    if eye is not None:
+        opt.flags |= _native.RT_RAYS_EYE
+        opt.eye[:] = [float(x) for x in np.asarray(eye, np.float32).reshape(3)]
+    opt.max_blocks = int(max_blocks)
+    opt.max_range = int(max_range)
+    return opt
+
+
+VIS_MAX_OBSERVERS = 32
+VIS_MAX_DIRECTION = 4095
+
+
+def pack_observers(observers, directions, dims):
+    """The observer records of a visibility field, an (n, 4) int32 array of x, y, z, kind: the point observers
+    ((n, 3) ix, iy, iz; kind 0) first, then the directions ((m, 3) integers towards the light; kind 1).  Either may
+    be None.  ValueError for what the C call rejects: none or more than 32 in all, a point off the lattice, a zero
+    direction or a component beyond +-4095."""
+    nx, ny, nz = (int(v) for v in dims)
+    rows = []
+    for given, kind in ((observers, _native.RT_VIS_POINT), (directions, _native.RT_VIS_DIRECTION)):
+        if given is None:
+            continue
+        a = np.asarray(given)
+        if a.size == 0:
+            continue
+        if a.ndim == 1 and a.size == 3:
+            a = a.reshape(1, 3)
+        if a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError("pack_observers: observers and directions are (n, 3) arrays")
+        if not np.issubdtype(a.dtype, np.integer):
+            if not np.all(np.asarray(a, np.float64) == np.rint(np.asarray(a, np.float64))):
+                raise ValueError("pack_observers: observers and directions are integers (see lattice_direction)")
+            a = np.rint(np.asarray(a, np.float64))
+        a = a.astype(np.int64)
+        if kind == _native.RT_VIS_POINT:
+            if (a < 0).any() or (a >= np.array([nx, ny, nz])).any():
+                raise ValueError("pack_observers: a point observer is not a point of the lattice")
+        else:
+            if (np.abs(a) > VIS_MAX_DIRECTION).any():
+                raise ValueError("pack_observers: a direction's component is beyond +-4095")
+            if (a == 0).all(axis=1).any():
+                raise ValueError("pack_observers: a direction is zero")
+        rows.append(np.concatenate([a, np.full((a.shape[0], 1), kind, np.int64)], axis=1))
+    n = sum(r.shape[0] for r in rows)
+    if n < 1 or n > VIS_MAX_OBSERVERS:
+        raise ValueError("pack_observers: 1..32 observers and directions in all")
+    return np.ascontiguousarray(np.concatenate(rows, axis=0), np.int32)
+
+
+def lattice_direction(world_dir, spacing, max_abs=255):
+    """The integer direction nearest a world vector in lattice terms, for visibility_field's directions:
+    round(max_abs * v / max|v|) with v_i = world_i / spacing_i, so its largest component is +-max_abs (1..4095).
+    ValueError for a zero spacing or a zero vector."""
+    w = np.asarray(world_dir, np.float64).reshape(3)
+    s = np.asarray(spacing, np.float64).reshape(3)
+    max_abs = int(max_abs)
+    if not 1 <= max_abs <= VIS_MAX_DIRECTION:
+        raise ValueError("lattice_direction: max_abs is 1..4095")
+    if (s == 0).any() or not np.isfinite(s).all():
+        raise ValueError("lattice_direction: a spacing is zero")
+    v = w / s
+    top = np.abs(v).max()
+    if not np.isfinite(v).all() or top == 0:
+        raise ValueError("lattice_direction: the vector is zero")
+    return tuple(int(c) for c in np.rint(max_abs * v / top))
+
 
 def path_scratch_bytes(origin, spacing, dims, clearance=0):
     """rt_terrain_path_scratch_bytes: the bytes of path_field_device's scratch block for a lattice and a clearance

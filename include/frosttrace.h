@@ -861,6 +861,75 @@ int rt_terrain_path_field_device(rt_compute cs, const rt_lattice* lat, const rt_
                                  const void* seeds_device, uint32_t n_seeds, void* scratch_device, size_t scratch_bytes,
                                  void* cost_device, void* flow_device, void* status_device);
 
+/* ---- visibility fields (ABI 9, additive; no reference counterpart) ----
+ * What can be seen from here, and what is lit: for every point of a lattice one bit per observer, set when the
+ * straight line between them is free of blocked cells.  Cover and lookout points, sensor and tower placement, a
+ * viewshed, the sun exposure of a whole volume.  Formed on the device from the occupancy bits alone, in integers, so
+ * the answer is exact; rt_terrain_trace_rays with ranges answers the same for one pair of points at sub-cell
+ * precision.
+ * The lattice is an rt_lattice exactly as rt_terrain_sample_lattice reads it; point index and occupancy word layout
+ *   as there.  A point is BLOCKED when its occupancy bit is set; the padding bits of a row's last word are ignored
+ *   whatever they hold.  The CELL of a lattice point c is the open unit box round it, |x - c| < 1/2 on each axis, in
+ *   lattice coordinates.
+ * Observers.  observers[0 .. n_observers), n_observers in 1..32, four int32 each: x, y, z, kind.
+ *   kind 0, a point observer: the lattice point (x, y, z), which must be a point of the lattice.
+ *   kind 1, a directional observer: the integer direction u = (x, y, z) TOWARDS the light (the sense of
+ *     SunDirection, along which the shadow ray travels); each |component| <= 4095, not all 0.
+ *   An invalid observer (another kind, a point off the lattice, a zero direction, a component out of range) is
+ *   RT_ERR_INVALID in the host form; the device form cannot check, so its kernel treats such an observer as seeing
+ *   nothing: its bit is 0 everywhere.
+ * Line of sight to a point observer o from the point p.  The cells BETWEEN them are the lattice points c, other than
+ *   o and p, whose cell meets the open segment from o to p: there is a t in (0, 1) with |o + t (p - o) - c| < 1/2
+ *   on all three axes.  Equivalently, as a walk: with d = p - o, axis i crosses a cell boundary at
+ *   t = (2 k + 1) / (2 |d_i|), k = 0 .. |d_i| - 1; take the distinct crossing times in ascending order; at each,
+ *   every axis that crosses then steps at once by sign(d_i) (a segment through a box edge or corner enters the
+ *   diagonal cell directly and does not visit the cells it only touches); the positions after each event but the
+ *   last are the cells between.  p SEES o iff no cell between is blocked.
+ *     The two endpoints are not tested: a blocked surface point that is met first is seen, a blocked observer cell
+ *     changes nothing, and p == o is seen.  The rule is symmetric in o and p.  Everything is decided in 32-bit
+ *     integers: (2 k + 1) / |d_i| against (2 j + 1) / |d_j| is (2 k + 1) |d_j| against (2 j + 1) |d_i|, both below
+ *     8191 * 4095 < 2^25.
+ * Line of sight to a directional observer u from p.  The same walk along p + t u for t > 0, crossings at
+ *   t = (2 k + 1) / (2 |u_i|), k = 0, 1, ... without end.  It stops at the first event whose position is not a point
+ *   of the lattice: p is LIT when the walk leaves the lattice without having met a blocked cell.  p itself is not
+ *   tested.
+ * max_range = R > 0.  Point observer: the bit is 0 when |p - o|^2 > R^2, and no walk runs.  Directional observer:
+ *   the walk also ends, lit, at the first visited cell c with |c - p|^2 > R^2; shadow casters beyond R do not
+ *   count.  R == 0: unbounded.  R bounds the work as well as the answer.  R > 2 * 4095 = 8190 would equal unbounded
+ *   (no two lattice points are farther apart) and is RT_ERR_INVALID.
+ * Result.  mask, a uint32 a point at index (iz * ny + iy) * nx + ix: bit k is 1 iff the point sees observer k; bits
+ *   n_observers .. 31 are 0.
+ * Status (4 uint32, may be NULL in both forms): [0] points with a non-zero mask; [1] the sum of the masks' set bits
+ *   (2^26 * 32 = 2^31 at most); [2] valid observers; [3] 0.
+ * occupancy_in NULL: the terrain's own occupancy, computed on the device into the scratch block as the distance
+ *   field does it (RT_RAYS_EYE and max_blocks as there, either kind of compute).
+ * occupancy_in not NULL: the caller's words in rt_terrain_sample_lattice's layout; the terrain is not evaluated.
+ * opt (NULL: the defaults) is an rt_visibility_options: size >= 28, flags RT_RAYS_EYE or 0, eye, max_blocks (the cap
+ *   of every pass's grid, 0: none), max_range (0: unbounded, 8190 at most).
+ * rt_terrain_visibility_scratch_bytes: the device form's scratch block for the lattice: its occupancy words and 64
+ *   bytes of counters, each part rounded up to 16 bytes; 0 for an invalid lattice or one without points.
+ * rt_terrain_visibility_field: host arrays; blocking.  It uploads the observers and any given occupancy and
+ *   downloads nothing but mask and status.
+ * rt_terrain_visibility_field_device: device arrays (4-byte aligned), enqueued on the compute's device stream; it
+ *   allocates nothing and never synchronises the host.  A NULL status_device is not written.
+ * Both: RT_ERR_INVALID for the lattice's errors (as rt_terrain_sample_lattice), a NULL compute or lattice,
+ *   opt->size < 28, flags other than RT_RAYS_EYE, max_range > 8190, n_observers outside 1..32, NULL observers or
+ *   mask, in the host form an invalid observer, and in the device form a scratch block that is NULL or below
+ *   rt_terrain_visibility_scratch_bytes; nothing is written then.  RT_ERR_STATE as for the distance field (texPerm2D
+ *   bound and the fail-safe word clear, with a given occupancy too).  A dims product of 0 is RT_OK and launches
+ *   nothing.  Like every query it reads no frame state and changes none.
+ * Out of scope: sub-cell or density-refined sight lines (rt_terrain_trace_rays with ranges); observers off the
+ *   lattice; more than 32 observers a call; soft visibility or a count of occluders; hierarchical or
+ *   distance-field skipping; an eye per point. */
+typedef struct { uint32_t size, flags; float eye[3]; uint32_t max_blocks; uint32_t max_range; } rt_visibility_options; /* 28 bytes, v1 */
+size_t rt_terrain_visibility_scratch_bytes(const rt_lattice* lat);
+int rt_terrain_visibility_field(rt_compute cs, const rt_lattice* lat, const rt_visibility_options* opt,
+                                const uint32_t* occupancy_in, const int32_t* observers, uint32_t n_observers,
+                                uint32_t* mask, uint32_t status[4]);
+int rt_terrain_visibility_field_device(rt_compute cs, const rt_lattice* lat, const rt_visibility_options* opt,
+                                       const void* occupancy_in_device, const void* observers_device, uint32_t n_observers,
+                                       void* scratch_device, size_t scratch_bytes, void* mask_device, void* status_device);
+
 /* ---- diagnostics (primitive-level parity tests; no reference counterpart) ----
  * rt_debug_math: device evaluation of the numeric primitives of DESIGN.md §Numerics
  *   (op 0 exp2, 1 log2, 2 exp, 3 sin, 4 cos, 5 sqrt, 6 rcp, 7 rsqrt, 8 pow, 9 max,
