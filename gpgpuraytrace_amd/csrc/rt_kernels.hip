@@ -3750,6 +3750,14 @@ __global__ void k_debug_math(int op, const float* __restrict__ a, const float* _
         y[i] = rts::sky_exit(a[3 * i], a[3 * i + 1], a[3 * i + 2]) ? 1.0f : 0.0f;
         return;
     }
+    if (op == 15) { // the AO direction about the normal a[3 i] for the key (px, py, a, k): the bits of b[4 i ..]
+        const f3 d = rts::ao_dir(rtm::mk(a[3 * i], a[3 * i + 1], a[3 * i + 2]), rtm::bits(b[4 * i]), rtm::bits(b[4 * i + 1]),
+                                 rtm::bits(b[4 * i + 2]), rtm::bits(b[4 * i + 3]));
+        y[3 * i] = d.x;
+        y[3 * i + 1] = d.y;
+        y[3 * i + 2] = d.z;
+        return;
+    }
     float x = a[i], v = 0.0f;
     switch (op) {
     case 0: v = rtm::exp2(x); break;

@@ -2768,6 +2768,25 @@ extern "C" int rt_debug_math(rt_device d, int op, const float* a, const float* b
         y[n] = std::nextafter((float)C, INFINITY); // ((float)C may round down)
         return RT_OK;
     }
+    if (op == 15) {
+        // the AO direction (rt_shader.h ao_dir) for n normals at a[3 i] and n keys (px, py, a, k), uint32 bit
+        // patterns at b[4 i]: out[3 i ..]
+        if (!b) return fail(RT_ERR_INVALID, "bad arguments");
+        const size_t na = (size_t)n * 12, nb = (size_t)n * 16;
+        HIP_TRY(hipMalloc(&da, na));
+        HIP_TRY(hipMalloc(&db, nb));
+        HIP_TRY(hipMalloc(&dy, na));
+        HIP_TRY(hipMemcpy(da, a, na, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(db, b, nb, hipMemcpyHostToDevice));
+        rt_launch_debug_math(d->stream, op, da, db, dy, n);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(d->stream));
+        HIP_TRY(hipMemcpy(y, dy, na, hipMemcpyDeviceToHost));
+        HIP_TRY(hipFree(da));
+        HIP_TRY(hipFree(db));
+        HIP_TRY(hipFree(dy));
+        return RT_OK;
+    }
     size_t bytes = (size_t)n * 4;
     HIP_TRY(hipMalloc(&da, bytes));
     HIP_TRY(hipMalloc(&db, bytes));

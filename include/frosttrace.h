@@ -942,6 +942,9 @@ int rt_terrain_visibility_field_device(rt_compute cs, const rt_lattice* lat, con
  *   next sample lies above the nomadplains ceiling, 256) for n triples (p.y, dir.y, dist) at a[3 i] (a: 3 n
  *   floats, b unused): out[i] = 1 or 0, and out[n] (out: n + 1 floats) = the ceiling the host computed for
  *   the product's octave constants, which must not exceed 256.
+ *   op 15 evaluates the AO extension's ray direction for n normals at a[3 i] (a: 3 n
+ *   floats, used as given) and n keys (px, py, AA sample, AO ray) at b[4 i] (b: 4 n uint32 passed as float bit
+ *   patterns, required): out[3 i ..] (out: 3 n floats) = the direction.
  * rt_debug_sky_ceiling (host only, no device): the nomadplains density's ceiling for n_oct octave weights
  *   np_rcp[0 .. n_oct) and the pow exponent, in double to *ceiling (may be NULL); returns 1 if the host
  *   would allow the sky exit with them (ceiling <= 256, and the n_grad float4 gradients at grad, if not

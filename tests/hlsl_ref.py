@@ -14,7 +14,10 @@ The march (traceRay, tracing.hlsl:32-105) is restated teacher-forced (march(), a
 branches and densities are read from the implementation under test, its own arithmetic is float64
 (tests/test_march_kat.py, tests/test_gpu_march_kat.py).  No stage marches by itself: the march's outcome is an
 input wherever one needs it (the shadow ray of getColor: whether it hit and its fcolord.w; traceSample's rr).
-Not restated: the AA resolve, AO and the camera matrices.  RECORDING changes only march constants.  Dead code of
+The AO extension (pcg_hash, ao_uv, ao_dir, ao_ray, ao_factor) and the AA resolve
+(tracescreen.hlsl:63-75: resolve) stand at the end of this module; the AO rays' occlusion is a march's outcome and
+an input like the shadow ray's (tests/test_ao_kat.py, tests/test_gpu_ao_kat.py).
+Not restated: the camera matrices.  RECORDING changes only march constants.  Dead code of
 the HLSL whose value never reaches a result is left out where it costs noise evaluations (getColor's blend, n1 and
 first FBM, color2, `s *= 30`; the `precision` of the shadow ray is a march input, restated by shadow_ray()); cheap
 dead terms are evaluated so that their literals stay in the table.
@@ -28,7 +31,10 @@ Every literal of getDensity, getFog and getColor has a name in LITERALS (its tex
 it stands); `tweak={name: value}` replaces it, which is how the mutation check of test_hlsl_kat.py shows that the
 bounds notice a misread constant; the march's literals ("march.*") and the shadow ray's ("<land>.shadow.*") stand
 in the same table.  Some tweaks are not numbers: "march.structure" names one of MARCH_STRUCTURES, and
-"<land>.color.swizzle" ("yxz" by default) names the coordinates of p that the colour FBM's three factors multiply.
+"<land>.color.swizzle" ("yxz" by default) names the coordinates of p that the colour FBM's three factors multiply;
+"ao.structure" and "resolve.structure" name one of AO_STRUCTURES and RESOLVE_STRUCTURES.  The AO hash's literals
+(INTEGER_LITERALS) are integers, printed in hexadecimal or decimal as DESIGN.md prints them, and are tweaked by
+Python integers.
 """
 import os
 
@@ -147,9 +153,10 @@ OCTAVE_BOUNDS = ("simple.density.octaves", "greenrocks.density.a_octaves", "gree
 
 
 def mutate(text):
-    """The literal with its last printed digit changed by one (up; a 9 goes down)."""
-    d = int(text[-1])
-    return text[:-1] + str(d + 1 if d < 9 else d - 1)
+    """The literal with its last printed digit changed by one (up; a 9 goes down, and the F of a hexadecimal one)."""
+    base = 16 if text.startswith("0x") else 10
+    d = int(text[-1], base)
+    return text[:-1] + "%X" % (d + 1 if d < base - 1 else d - 1)
 
 
 def mutants(prefix):
@@ -158,6 +165,9 @@ def mutants(prefix):
     coordinates under the small factors."""
     for name, (text, _) in LITERALS.items():
         if name.startswith(prefix + "."):
+            if name in INTEGER_LITERALS:
+                yield name, {name: int(mutate(text), 0)}
+                continue
             yield name, {name: f32(mutate(text))}
             if name in OCTAVE_BOUNDS:
                 yield name + "+1", {name: f32(text) + 1.0}
@@ -177,6 +187,16 @@ class _K:
         if full in self.tweak:
             return np.float64(self.tweak[full])
         return f32(LITERALS[full][0])
+
+    def integer(self, name):
+        full = self.prefix + "." + name
+        assert full in INTEGER_LITERALS, full
+        return int(self.tweak[full]) if full in self.tweak else int(LITERALS[full][0], 0)
+
+    def structure(self, allowed):
+        s = self.tweak.get(self.prefix + ".structure")
+        assert s is None or s in allowed, s
+        return s
 
     def swizzle(self):
         return self.tweak.get(self.prefix + ".swizzle", "yxz")
@@ -464,13 +484,13 @@ MARCH_STRUCTURES = {
 }
 MARCH_FOG = ("march.mid_half", "march.structure=no_fog_refund", "march.structure=fog_by_laststep")
 TIE_BAND = 1e-5
-STRUCTURES = ("march.structure",)
+STRUCTURES = ("march.structure", "ao.structure", "resolve.structure")
 
 
 def _march_mutants(prefix):
-    if prefix == "march":
-        for s in MARCH_STRUCTURES:
-            yield "march.structure=" + s, {"march.structure": s}
+    """The structural misreadings of a prefix that has some: "<prefix>.structure=<name>"."""
+    for s in {"march": MARCH_STRUCTURES, "ao": AO_STRUCTURES, "resolve": RESOLVE_STRUCTURES}.get(prefix, ()):
+        yield prefix + ".structure=" + s, {prefix + ".structure": s}
 
 
 def shadow_ray(land, dist, tweak=None):
@@ -577,3 +597,144 @@ def march(land, p, dir, dist0, enddist, stepmod, recording, calcfog, skiprefine,
         at = np.where(r, dist_obs[k], at)
         record(k + 1, at)
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# The AO extension and the AA resolve (tracescreen.hlsl:63-75).  AO has no shader to follow:
+# its definition is the paragraph of DESIGN.md, read here on its own.  The hash is integer arithmetic mod 2^32
+# (Python integers, or uint64 arrays masked to 32 bits); everything after it is float64 with real sqrt, sin, cos
+# and 2 pi.
+_T = "DESIGN.md section 9"
+_lits("ao", _T + ", the key", key_px="0x9E3779B1", key_py="0x85EBCA77", key_k="0xC2B2AE3D", pack="16")
+_lits("ao", _T + ", pcg_hash", pcg_mul="747796405", pcg_add="2891336453", pcg_out="277803737", shift_top="28",
+      shift_base="4", shift_out="22")
+_lits("ao", _T + ", u1 and u2", shift_u="8")
+_lits("ao", _T + ", the basis", up_switch="0.9", up_steep_x="0.0", up_steep_y="1.0", up_steep_z="0.0", up_x="1.0",
+      up_y="0.0", up_z="0.0")
+_lits("ao", _T + ", the ray", start="0.4", end="25")
+_lits("ao", _T + ", the factor", strength="0.6")
+_lits("resolve", "common/shaders/tracescreen.hlsl:63", start="0.0")
+_lits("resolve", "common/shaders/tracescreen.hlsl:75", alpha="1.0")
+INTEGER_LITERALS = tuple("ao." + k for k in ("key_px", "key_py", "key_k", "pack", "pcg_mul", "pcg_add", "pcg_out",
+                                             "shift_top", "shift_base", "shift_out", "shift_u"))
+AO_STRUCTURES = {
+    "swap_u": "u1 and u2 exchanged",
+    "uniform_hemisphere": "sz = 1 - u1, r = sqrt(1 - sz^2): uniform over the hemisphere, not cosine-weighted",
+    "rehash_key": "h2 = pcg(key + 1), not pcg(h)",
+    "left_handed": "ty = tx x n",
+    "k_major": "k * 16 + a in the key",
+    "swap_pixel": "px and py exchanged in the key",
+    "fog_on": "the AO ray marched with fog on",
+    "refine": "the AO ray marched with skiprefine off",
+}
+RESOLVE_STRUCTURES = {
+    "ao_inside_saturate": "saturate(c * ao)",
+    "ao_on_misses": "the AO factor applied to sky samples too",
+    "saturate_after_mean": "saturate(sum c_a / A)",
+}
+_M32 = 0xFFFFFFFF
+
+
+def _words(x):
+    """(x, the constructor of a constant): Python integers stay so; arrays become uint64, whose products of two
+    32-bit words cannot overflow."""
+    if isinstance(x, np.ndarray):
+        return x.astype(np.uint64), np.uint64
+    return int(x), int
+
+
+def pcg_hash(x, tweak=None):
+    """pcg_hash of 32-bit words: st = x * 747796405 + 2891336453; w = ((st >> ((st >> 28) + 4)) ^ st) * 277803737;
+    (w >> 22) ^ w, all mod 2^32.  x: a Python integer or an integer array (any shape, at least 1-d)."""
+    K = _K("ao", tweak)
+    x, c = _words(x)
+    m = c(_M32)
+    st = (x * c(K.integer("pcg_mul")) + c(K.integer("pcg_add"))) & m
+    w = (((st >> ((st >> c(K.integer("shift_top"))) + c(K.integer("shift_base")))) ^ st) * c(K.integer("pcg_out"))) & m
+    return ((w >> c(K.integer("shift_out"))) ^ w) & m
+
+
+def ao_key(px, py, a, k, tweak=None):
+    """(px * 0x9E3779B1) ^ (py * 0x85EBCA77) ^ ((a * 16 + k) * 0xC2B2AE3D) mod 2^32."""
+    K = _K("ao", tweak)
+    s = K.structure(AO_STRUCTURES)
+    (px, c), py, a, k = _words(px), _words(py)[0], _words(a)[0], _words(k)[0]
+    if s == "swap_pixel":
+        px, py = py, px
+    if s == "k_major":
+        a, k = k, a
+    m = c(_M32)
+    return ((((px & m) * c(K.integer("key_px"))) & m) ^ (((py & m) * c(K.integer("key_py"))) & m)
+            ^ (((a * c(K.integer("pack")) + k) * c(K.integer("key_k"))) & m))
+
+
+def ao_uv(px, py, a, k, tweak=None):
+    """(u1, u2) of AO ray k of AA sample a of pixel (px, py): the top 24 bits of two successive hashes, over 2^24."""
+    K = _K("ao", tweak)
+    s = K.structure(AO_STRUCTURES)
+    key = ao_key(px, py, a, k, tweak)
+    h = pcg_hash(key, tweak)
+    h2 = pcg_hash((key + 1) & _words(key)[1](_M32), tweak) if s == "rehash_key" else pcg_hash(h, tweak)
+    shift = _words(h)[1](K.integer("shift_u"))
+    u1, u2 = ((np.asarray(v >> shift).astype(np.float64)) * 2.0 ** -24 for v in (h, h2))
+    return (u2, u1) if s == "swap_u" else (u1, u2)
+
+
+def ao_dir(n, px, py, a, k, tweak=None):
+    """The direction of that AO ray about the normal n (m, 3), used as given: (m, 3) float64."""
+    K = _K("ao", tweak)
+    s = K.structure(AO_STRUCTURES)
+    n = _vec(n)
+    u1, u2 = ao_uv(px, py, a, k, tweak)
+    r, sz = np.sqrt(u1), np.sqrt(1.0 - u1)
+    if s == "uniform_hemisphere":
+        sz = 1.0 - u1
+        r = np.sqrt(1.0 - sz * sz)
+    phi = u2 * (2.0 * np.pi)
+    sx, sy = r * np.cos(phi), r * np.sin(phi)
+    steep = np.abs(n[:, 0]) > K("up_switch")
+    up = np.where(steep[:, None], _col(K("up_steep_x"), K("up_steep_y"), K("up_steep_z"))[None, :],
+                  _col(K("up_x"), K("up_y"), K("up_z"))[None, :])
+    tx = np.cross(up, n)
+    tx = tx / np.linalg.norm(tx, axis=1, keepdims=True)
+    ty = np.cross(tx, n) if s == "left_handed" else np.cross(n, tx)
+    return tx * np.reshape(sx, (-1, 1)) + ty * np.reshape(sy, (-1, 1)) + n * np.reshape(sz, (-1, 1))
+
+
+def ao_ray(dist, tweak=None, land="nomadplains"):
+    """The arguments of an AO ray's march from a hit at `dist`: (dist0, enddist, stepmod (n,), calcfog, skiprefine,
+    max_steps) of traceRay(hit, 0.4, 25, the shadow ray's precision, dir, no fog, skiprefine), with no step cap."""
+    K = _K("ao", tweak)
+    s = K.structure(AO_STRUCTURES)
+    return K("start"), K("end"), shadow_ray(land, dist)[2], s == "fog_on", s != "refine", 0
+
+
+def ao_factor(occ, samples, tweak=None):
+    """1 - 0.6 * occ / K for occ occluded rays of K."""
+    K = _K("ao", tweak)
+    return 1.0 - K("strength") * np.asarray(occ, np.float64) / float(samples)
+
+
+def resolve(samples, ao, hit, tweak=None):
+    """CSMain's pixel (tracescreen.hlsl:63-75) with the AO extension: samples (n, A, 3) traceSample's colours, ao
+    (n, A) each sample's AO factor (read for the hits alone), hit (n, A).  sum_a saturate(c_a) * (ao_a if hit_a else
+    1) / A, alpha 1: (n, 4)."""
+    K = _K("resolve", tweak)
+    s = K.structure(RESOLVE_STRUCTURES)
+    c = np.asarray(samples, np.float64)
+    n, count = c.shape[:2]
+    assert c.shape == (n, count, 3)
+    ao, hit = np.asarray(ao, np.float64).reshape(n, count), np.asarray(hit, bool).reshape(n, count)
+    f = (ao if s == "ao_on_misses" else np.where(hit, ao, 1.0))[:, :, None]
+    color = np.full((n, 3), K("start"))  # :63
+    for a in range(count):  # :67-72
+        if s == "saturate_after_mean":
+            color = color + c[:, a] * f[:, a]
+        elif s == "ao_inside_saturate":
+            color = color + _sat(c[:, a] * f[:, a])
+        else:
+            color = color + _sat(c[:, a]) * f[:, a]
+    color = color / float(count)  # :74
+    if s == "saturate_after_mean":
+        color = _sat(color)
+    return np.concatenate([color, np.full((n, 1), K("alpha"))], axis=1)  # :75

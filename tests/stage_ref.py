@@ -1,7 +1,7 @@
 """The oracle's shading stages at inputs of the caller's own (TEST INFRASTRUCTURE): builds, binds and caches
 tests/tools/stage_ref.c, which includes the oracle's source and exports its static get_normal, get_fog,
-get_pixel_ray, get_color and trace_ray, and its AA offset tables.  Built with the oracle's own flags into
-tests/tools/_build/."""
+get_pixel_ray, get_color and trace_ray, its AA offset tables, and of the AO extension pcg_hash, ao_dir, the factor
+and trace_sample.  Built with the oracle's own flags into tests/tools/_build/."""
 import ctypes as C
 import os
 import subprocess
@@ -43,6 +43,14 @@ def lib():
         L.st_shadow_precision.restype = None
         L.st_aa_offsets.argtypes = [C.c_int, fp]
         L.st_aa_offsets.restype = C.c_int
+        L.st_pcg_hash.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+        L.st_pcg_hash.restype = None
+        L.st_ao_dir.argtypes = [fp, C.c_void_p, C.c_int64, fp]
+        L.st_ao_dir.restype = None
+        L.st_ao_factor.argtypes = [C.c_int, C.c_int]
+        L.st_ao_factor.restype = C.c_float
+        L.st_trace_samples.argtypes = [nzp, frp, fp, fp, fp, C.c_void_p, C.c_int64, fp, fp, fp, fp]
+        L.st_trace_samples.restype = None
         _lib = L
     return _lib
 
@@ -116,6 +124,45 @@ def aa_offsets(samples):
     out = np.zeros((16, 2), np.float32)
     n = lib().st_aa_offsets(int(samples), O._fp(out))
     return out[:n].copy()
+
+
+def pcg_hash(x):
+    """The oracle's pcg_hash of uint32 words: uint32, the shape of x."""
+    x = np.ascontiguousarray(x, np.uint32)
+    out = np.zeros_like(x)
+    lib().st_pcg_hash(x.ctypes.data, x.size, out.ctypes.data)
+    return out
+
+
+def ao_dir(normals, keys):
+    """The oracle's ao_dir for normals (n, 3), used as given, and keys (n, 4) uint32 (px, py, a, k): (n, 3) float32."""
+    nr = _a(normals, 3)
+    keys = np.ascontiguousarray(keys, np.uint32).reshape(-1, 4)
+    assert len(keys) == len(nr)
+    out = np.zeros((len(nr), 3), np.float32)
+    lib().st_ao_dir(O._fp(nr), keys.ctypes.data, len(nr), O._fp(out))
+    return out
+
+
+def ao_factor(occ, samples):
+    """ambient_occlusion's factor for occ occluded rays of samples: a float32."""
+    return np.float32(lib().st_ao_factor(int(occ), int(samples)))
+
+
+def trace_samples(consts, land, p, dir, ranges, keys, aa=1, ao=0, max_steps=0):
+    """The oracle's trace_sample for n rays as ro_tracescreen calls it for the frame of consts (oracle_lib.make_frame's
+    dict) with these macros: p, dir (n, 3); ranges (n, 2) plane.x, plane.y; keys (n, 3) uint32 (px, py, a).
+    (colour (n, 3), not saturated; ao (n,): 1 for a miss; the primary march's pd (n, 4) and density (n,)) float32."""
+    p, dir, ranges = _a(p, 3), _a(dir, 3), _a(ranges, 2)
+    keys = np.ascontiguousarray(keys, np.uint32).reshape(-1, 3)
+    n = len(p)
+    assert len(dir) == n and len(ranges) == n and len(keys) == n
+    col, f, pd, dens = (np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros((n, 4), np.float32),
+                        np.zeros(n, np.float32))
+    fr = O.make_frame(consts, landscape=O.LANDSCAPES[land], aa=aa, ao=ao, max_steps=max_steps)
+    lib().st_trace_samples(C.byref(O.noise_tables()), C.byref(fr), O._fp(p), O._fp(dir), O._fp(ranges), keys.ctypes.data,
+                           n, O._fp(col), O._fp(f), O._fp(pd), O._fp(dens))
+    return col, f, pd, dens
 
 
 def shadow_precision(dist):
