@@ -3758,7 +3758,13 @@ __global__ void k_debug_math(int op, const float* __restrict__ a, const float* _
         y[3 * i + 2] = d.z;
         return;
     }
-    float x = a[i], v = 0.0f;
+    // op 16, the sweep: a = 4 uint32 words (start pattern, odd multiplier, element op, mask), x = the float with
+    // bits (start + i * multiplier) & mask, evaluated with the element op and b[0]; no input array
+    const bool sweep = op == 16;
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(a);
+    const int j = sweep ? 0 : i;
+    float x = sweep ? rtm::fbits((w[0] + (uint32_t)i * w[1]) & w[3]) : a[i], v = 0.0f;
+    if (sweep) op = (int)w[2];
     switch (op) {
     case 0: v = rtm::exp2(x); break;
     case 1: v = rtm::log2(x); break;
@@ -3768,11 +3774,12 @@ __global__ void k_debug_math(int op, const float* __restrict__ a, const float* _
     case 5: v = rtm::sqrt(x); break;
     case 6: v = rtm::rcp(x); break;
     case 7: v = rtm::rcp(rtm::sqrt(x)); break;
-    case 8: v = rtm::pow(x, b[i]); break;
-    case 9: v = rtm::max(x, b[i]); break;
-    case 10: v = rtm::min(x, b[i]); break;
-    case 11: v = rtm::pow_nonneg(x, b[i]); break;
-    case 13: v = rtm::pow_nonneg_wave(x, b[i]); break; // (a wave = 64 consecutive elements)
+    case 8: v = rtm::pow(x, b[j]); break;
+    case 9: v = rtm::max(x, b[j]); break;
+    case 10: v = rtm::min(x, b[j]); break;
+    case 11: v = rtm::pow_nonneg(x, b[j]); break;
+    case 13: v = rtm::pow_nonneg_wave(x, b[j]); break; // (a wave = 64 consecutive elements)
+    case 17: v = rtm::log2_nonneg(x); break;
     default: v = 0.0f; break;
     }
     y[i] = v;

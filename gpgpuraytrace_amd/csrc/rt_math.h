@@ -8,8 +8,12 @@
 //   * a*b+c forms of the HLSL source are single fused multiply-adds (fxc `mad`);
 //   * a/b is a * rcp(b) with a correctly rounded rcp (D3D `div` = rcp+mul);
 //   * sqrt is correctly rounded; normalize(v) = v * rcp(sqrt(dot(v,v)));
-//   * exp2/log2/sin/cos are the fixed polynomials below (1-2 ulp), pow(x,y) =
-//     exp2(y*log2(x)), exp(x) = exp2(x*log2(e));
+//   * exp2/log2/sin/cos are the fixed polynomials below, pow(x,y) = exp2(y*log2(x)),
+//     exp(x) = exp2(x*log2(e)).  Measured against double libm over every float32 input
+//     (tests/test_prim_sweep.py test_accuracy_exhaustive): exp2 0.952 ulp
+//     on [-150, 128), log2 1.086 ulp on finite x > 0 (an ulp no smaller than 2^-24), sin and
+//     cos 7.43e-8 absolute on |x| <= 1e5; exp and pow inherit |y log2 x| times the rounding
+//     of exp2's argument (64 ulp for exp near 87, about 111 ulp for pow at the range's ends);
 //   * max/min are IEEE-754-2019 maximumNumber/minimumNumber (v_max_f32).
 // Build every translation unit that includes this with -ffp-contract=off.
 #pragma once

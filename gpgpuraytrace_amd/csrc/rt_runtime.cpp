@@ -2787,6 +2787,31 @@ extern "C" int rt_debug_math(rt_device d, int op, const float* a, const float* b
         HIP_TRY(hipFree(dy));
         return RT_OK;
     }
+    if (op == 16) {
+        // the sweep: a = 4 uint32 words (start pattern, odd multiplier, element op, mask), b[0] = the pow ops'
+        // second operand; the kernel makes its n inputs from them, so only the words and n results are allocated
+        uint32_t w[4];
+        memcpy(w, a, sizeof w);
+        const bool unary = w[2] <= 7u || w[2] == 17u;
+        if (!(unary || w[2] == 8u || w[2] == 11u || w[2] == 13u) || !(w[1] & 1u) || (!unary && !b))
+            return fail(RT_ERR_INVALID, "bad sweep arguments");
+        const float y0 = b ? b[0] : 0.0f;
+        const size_t out = (size_t)n * 4;
+        HIP_TRY(hipMalloc(&da, sizeof w));
+        HIP_TRY(hipMalloc(&db, 4));
+        HIP_TRY(hipMalloc(&dy, out));
+        // on the kernel's own stream, like op 12's memset (every result is written: none is needed here)
+        HIP_TRY(hipMemcpyAsync(da, w, sizeof w, hipMemcpyHostToDevice, d->stream));
+        HIP_TRY(hipMemcpyAsync(db, &y0, 4, hipMemcpyHostToDevice, d->stream));
+        rt_launch_debug_math(d->stream, op, da, db, dy, n);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(y, dy, out, hipMemcpyDeviceToHost, d->stream));
+        HIP_TRY(hipStreamSynchronize(d->stream));
+        HIP_TRY(hipFree(da));
+        HIP_TRY(hipFree(db));
+        HIP_TRY(hipFree(dy));
+        return RT_OK;
+    }
     size_t bytes = (size_t)n * 4;
     HIP_TRY(hipMalloc(&da, bytes));
     HIP_TRY(hipMalloc(&db, bytes));

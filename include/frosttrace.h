@@ -934,7 +934,7 @@ int rt_terrain_visibility_field_device(rt_compute cs, const rt_lattice* lat, con
  * rt_debug_math: device evaluation of the numeric primitives of DESIGN.md §Numerics
  *   (op 0 exp2, 1 log2, 2 exp, 3 sin, 4 cos, 5 sqrt, 6 rcp, 7 rsqrt, 8 pow, 9 max,
  *   10 min, 11 pow for x >= 0, 13 the march's wave-tested pow for x >= 0: a wave is 64
- *   consecutive elements); host arrays of n floats (b may be NULL for unary ops).
+ *   consecutive elements, 17 log2 for finite x >= 0); host arrays of n floats (b may be NULL for unary ops).
  *   op 12 sweeps the nomadplains octave-count estimate over the n floats whose bit
  *   patterns follow bits(a[0]) and writes 3 uint32 to out: unflagged estimates that differ
  *   from the exact count, flagged estimates, patterns swept.
@@ -945,6 +945,13 @@ int rt_terrain_visibility_field_device(rt_compute cs, const rt_lattice* lat, con
  *   op 15 evaluates the AO extension's ray direction for n normals at a[3 i] (a: 3 n
  *   floats, used as given) and n keys (px, py, AA sample, AO ray) at b[4 i] (b: 4 n uint32 passed as float bit
  *   patterns, required): out[3 i ..] (out: 3 n floats) = the direction.
+ *   op 16 sweeps one element op over n inputs that the kernel makes itself (no input array is allocated or
+ *   copied): a = 4 uint32 words passed as float bit patterns (start pattern, odd multiplier, element op, mask),
+ *   b[0] = the second operand of the pow ops (b may be NULL for the unary ones); input i is the float with the
+ *   bit pattern (start + i * multiplier mod 2^32) & mask (mask 0xffffffff, or 0x7fffffff for x >= 0), and out[i]
+ *   (out: n floats) = the element op of it.  Element ops: 0-8, 11, 13 and 17; a wave is still 64 consecutive
+ *   elements, so op 13 under a multiplier other than 1 sees mixed magnitudes in one wave.
+ *   op 17 is log2 for finite x >= 0 (the shading's mip level), an ordinary unary op and an element op of 16.
  * rt_debug_sky_ceiling (host only, no device): the nomadplains density's ceiling for n_oct octave weights
  *   np_rcp[0 .. n_oct) and the pow exponent, in double to *ceiling (may be NULL); returns 1 if the host
  *   would allow the sky exit with them (ceiling <= 256, and the n_grad float4 gradients at grad, if not
