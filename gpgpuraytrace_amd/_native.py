@@ -101,6 +101,14 @@ class RtVisibilityOptions(C.Structure):
                 ("max_range", C.c_uint32)]
 
 
+RT_REGION_NONE = 0xFFFFFFFF  # the label of a point that is no member
+
+
+class RtRegionOptions(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("eye", C.c_float * 3), ("max_blocks", C.c_uint32),
+                ("clearance_cells", C.c_uint32), ("connectivity", C.c_uint32), ("state", C.c_uint32)]
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -219,6 +227,12 @@ SIGNATURES = {
                                          _vp, _vp]),
     "rt_terrain_visibility_field_device": (_i, [_vp, C.POINTER(RtLattice), C.POINTER(RtVisibilityOptions), _vp, _vp,
                                                 C.c_uint32, _vp, _sz, _vp, _vp]),
+    # region fields: for every point of a lattice the smallest point index (uint32) of its connected region of free
+    # or of blocked points, the region's size (uint32) and four status words; the device form takes its scratch block
+    "rt_terrain_region_scratch_bytes": (_sz, [C.POINTER(RtLattice), C.POINTER(RtRegionOptions)]),
+    "rt_terrain_region_field": (_i, [_vp, C.POINTER(RtLattice), C.POINTER(RtRegionOptions), _vp, _vp, _vp, _vp]),
+    "rt_terrain_region_field_device": (_i, [_vp, C.POINTER(RtLattice), C.POINTER(RtRegionOptions), _vp, _vp, _sz, _vp,
+                                            _vp, _vp]),
     "rt_noise_generate": (_i, [C.c_uint32, _i, _vp, _vp]),
     "rt_terrain_set_target_depths": (_i, [_vp, _vp]),
     "rt_recorder_create": (_i, [_vp, _i, _i, _cp, C.POINTER(_vp)]),

@@ -312,6 +312,29 @@ struct RtVisibilityQuery {
 };
 bool rt_launch_visibilityquery(const RtLaunch& a, const RtVisibilityQuery& q);
 
+// A region field's passes (rt_terrain_region_field; the definition is in include/frosttrace.h, the forest, find and
+// unite and the scratch layout in rt_rayquery.h), enqueued on a.stream: k_regionlocal (the member words from
+// `occupancy` and, if not null, `d2`; every tile labelled on its own), k_regionmerge, k_regionflatten and, when
+// `counts` is not null, k_regionfinish.  member: the lattice's word count; counts: a word a point, or null when
+// neither `size` nor `status` is asked for (both null then): nothing is counted and k_regionfinish is not launched.
+// counters: rtq::REGION_CNT_WORDS words that are 0 when the first kernel starts, zeroed on a.stream by the caller.
+// solid: members are the blocked points (d2 null).  faces: connectivity 6.  All dims >= 1 with a product of 2^26
+// at most.  false: nothing launched.
+struct RtRegionQuery {
+    const uint32_t* occupancy;
+    const uint32_t* d2;
+    uint32_t* member;
+    uint32_t* counts;
+    uint32_t* counters;
+    uint32_t dims[3];
+    bool solid, faces;
+    uint32_t* label;
+    uint32_t* size;
+    uint32_t* status;
+    uint32_t tile_blocks, point_blocks;
+};
+bool rt_launch_regionquery(const RtLaunch& a, const RtRegionQuery& q);
+
 #define RT_TILE 32
 #define RT_FIN_SLOTS 1536 // k_trace's fin pool slots per block
 #define RT_AO_POOL_SLOTS 256 // k_trace's AO counter slots per block (LDS) and their colours (cpool)

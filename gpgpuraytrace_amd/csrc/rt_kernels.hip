@@ -3464,6 +3464,21 @@ __device__ __forceinline__ void path_mark(uint32_t* flags, uint32_t* active, con
     if (atomicExch(f, 1u) == 0u) atomicAdd(active, 1u);
 }
 
+// Word w = row * words + j of the passable words: not blocked, a point that exists, and with a clearance (d2 not
+// null) a far d2.  k_pathinit and k_regionlocal form their words with it.
+__device__ __forceinline__ uint32_t path_passable_word(const uint32_t* __restrict__ occ, const uint32_t* __restrict__ d2,
+                                                       uint32_t nx, uint32_t row, uint32_t j, uint32_t w)
+{
+    uint32_t open = ~occ[w] & rtq::dist_valid_bits(nx, j);
+    if (d2) {
+        const uint32_t* __restrict__ r = d2 + (size_t)row * nx + 32u * j;
+        const uint32_t seen = open;
+        for (uint32_t b = 0; b < 32u; ++b)
+            if (((seen >> b) & 1u) && r[b] != rtq::kDistFar) open &= ~(1u << b);
+    }
+    return open;
+}
+
 // the passable words (not blocked, a point that exists, and with a clearance a far d2), every cost far, the tile
 // flags, the counters and the status cleared
 __global__ void __launch_bounds__(rtq::kDistThreads) k_pathinit(const uint32_t* __restrict__ occ, const uint32_t* __restrict__ d2,
@@ -3479,14 +3494,7 @@ __global__ void __launch_bounds__(rtq::kDistThreads) k_pathinit(const uint32_t* 
     if (first < 4u) status[first] = 0u;
     for (uint32_t w = first; w < all_words; w += stride) {
         const uint32_t row = w / words, j = w - row * words;
-        uint32_t open = ~occ[w] & rtq::dist_valid_bits(g.nx, j);
-        if (d2) {
-            const uint32_t* __restrict__ r = d2 + (size_t)row * g.nx + 32u * j;
-            const uint32_t seen = open;
-            for (uint32_t b = 0; b < 32u; ++b)
-                if (((seen >> b) & 1u) && r[b] != rtq::kDistFar) open &= ~(1u << b);
-        }
-        passable[w] = open;
+        passable[w] = path_passable_word(occ, d2, g.nx, row, j, w);
     }
 }
 
@@ -3717,6 +3725,291 @@ bool rt_launch_visibilityquery(const RtLaunch& a, const RtVisibilityQuery& q)
     const VisParams p{q.dims[0], q.dims[1], q.dims[2], (uint32_t)points, q.range2, q.n_observers};
     hipLaunchKernelGGL(k_visibility, dim3(q.blocks), dim3(rtq::kDistThreads), 0, a.stream, q.occupancy, q.observers, q.mask,
                        q.counters, p);
+    return true;
+}
+
+// ---------------------------------------------------------------------------
+// Region fields (rt_terrain_region_field): for every point the smallest point index of its connected region of
+// members, the free (passable) or the blocked points (include/frosttrace.h has the definition, rt_rayquery.h the
+// forest, region_find / region_unite and the scratch layout).  A union-find with `label` as the forest, in a fixed
+// number of launches: no sweeps, nothing to converge.
+//
+// What the kernels keep:
+//  * A forest word only ever falls, and only to the index of a point of the same final region.  A stale read is
+//    therefore a read of an older ancestor: it costs steps, never correctness.
+//  * In k_regionmerge and k_regionflatten every access to a forest word that another workgroup may write is an
+//    atomic read-modify-write (atomicMin) or a relaxed load / store at agent scope (RegionForest below, and the
+//    store of k_regionflatten).  The member words and, in k_regionfinish, the labels and counts are written by an
+//    earlier launch only and are read plainly.
+//  * Stream order is the only barrier between the launches.  No workgroup waits for a value another must write: no
+//    spin, no cooperative launch, no grid barrier.
+//  * Every loop has a strictly decreasing integer as its variant (a point index, a root, the points of a tile still
+//    to settle) and a hard bound derived from it, the lattice's points at most; a bound that is hit bumps
+//    REGION_CNT_FAULT, which clears status[0], and leaves the loop.  Every kernel ends whatever the words hold.
+//  * No kernel uses scratch memory.
+namespace {
+
+struct RegionGrid {
+    uint32_t nx, ny, nz, points;
+    uint32_t tnx, tny, tnz, tiles;
+    uint32_t faces; // 1: connectivity 6, the face moves only
+};
+
+// the forest words on the device: rtq::region_find's and region_unite's access policy
+struct RegionForest {
+    uint32_t* w;
+    uint32_t* faults;
+    __device__ __forceinline__ uint32_t load(uint32_t i) { return __hip_atomic_load(w + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+    __device__ __forceinline__ uint32_t fall(uint32_t i, uint32_t v) { return atomicMin(w + i, v); }
+    __device__ __forceinline__ void fault() { atomicAdd(faults, 1u); }
+};
+
+// the halo index of the tile's thread (point) l
+__device__ __forceinline__ uint32_t region_halo_index(uint32_t l)
+{
+    const uint32_t lx = l % rtq::kPathTileX, ly = l / rtq::kPathTileX % rtq::kPathTileY, lz = l / (rtq::kPathTileX * rtq::kPathTileY);
+    return ((lz + 1u) * rtq::kPathHaloY + ly + 1u) * rtq::kPathHaloX + lx + 1u;
+}
+
+// One block a tile.  The tile's 16 member words (path_passable_word, or the blocked points that exist), then the
+// tile's members labelled in LDS to their local fixed point: every member takes the minimum over its linked members
+// in the tile and jumps along the labels (a label is the thread index of a member of the same local component that
+// is not above the point), until no label falls.  After k passes every member within k links of its component's
+// minimum holds it, and a tile has 512 points, so 512 passes are enough and the bound cannot be hit.  label[p] is
+// the global index of the tile-local root, kRegionNone at a non-member: a forest with label[p] <= p.  The count
+// words (when something is counted) and the status are zeroed here.  The halo of the LDS tile stays kRegionNone.
+__global__ void __launch_bounds__(rtq::kPathTilePoints) k_regionlocal(const uint32_t* __restrict__ occ, const uint32_t* __restrict__ d2,
+                                                                     uint32_t* __restrict__ member, uint32_t* __restrict__ label,
+                                                                     uint32_t* __restrict__ counts, uint32_t* counters,
+                                                                     uint32_t* status, uint32_t solid, RegionGrid g)
+{
+    __shared__ uint32_t c[rtq::kPathHaloPoints];
+    __shared__ uint32_t mw[rtq::kPathTileY * rtq::kPathTileZ];
+    const uint32_t tid = threadIdx.x, words = (g.nx + 31u) / 32u;
+    const uint32_t lx = tid % rtq::kPathTileX, ly = tid / rtq::kPathTileX % rtq::kPathTileY,
+                   lz = tid / (rtq::kPathTileX * rtq::kPathTileY);
+    const uint32_t me = region_halo_index(tid);
+    if (status && blockIdx.x == 0 && tid < 4u) status[tid] = 0u;
+    for (uint32_t h = tid; h < rtq::kPathHaloPoints; h += rtq::kPathTilePoints) c[h] = rtq::kRegionNone;
+    for (uint32_t t = blockIdx.x; t < g.tiles; t += gridDim.x) {
+        const uint32_t tx = t % g.tnx, ty = t / g.tnx % g.tny, tz = t / (g.tnx * g.tny);
+        const uint32_t x0 = tx * rtq::kPathTileX, y0 = ty * rtq::kPathTileY, z0 = tz * rtq::kPathTileZ;
+        const uint32_t ix = x0 + lx, iy = y0 + ly, iz = z0 + lz;
+        const bool exists = ix < g.nx && iy < g.ny && iz < g.nz;
+        const uint32_t row = iz * g.ny + iy;
+        __syncthreads(); // the tile before is done with c and mw
+        if (lx == 0u) {
+            uint32_t m = 0u;
+            if (iy < g.ny && iz < g.nz) {
+                const uint32_t w = row * words + tx;
+                m = solid ? occ[w] & rtq::dist_valid_bits(g.nx, tx) : path_passable_word(occ, d2, g.nx, row, tx, w);
+                member[w] = m;
+            }
+            mw[tid / rtq::kPathTileX] = m;
+        }
+        __syncthreads();
+        const bool in = (mw[tid / rtq::kPathTileX] >> lx) & 1u; // (a member exists: the words hold no padding bit)
+        uint32_t mine = in ? tid : rtq::kRegionNone;
+        c[me] = mine;
+        __syncthreads();
+        bool settled = false;
+        for (uint32_t pass = 0; pass < rtq::kPathTilePoints; ++pass) {
+            uint32_t best = mine;
+            if (in) {
+#pragma unroll
+                for (int dz = -1; dz <= 1; ++dz)
+#pragma unroll
+                    for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+                        for (int dx = -1; dx <= 1; ++dx) {
+                            const int k = (dx != 0) + (dy != 0) + (dz != 0);
+                            if (k == 0 || (k > 1 && g.faces)) continue;
+                            const uint32_t v = c[(int)me + (dz * (int)rtq::kPathHaloY + dy) * (int)rtq::kPathHaloX + dx];
+                            best = min(best, v); // (kRegionNone at a non-member and in the halo)
+                        }
+                // jump along the labels: best strictly falls, nine halvings of 512 at most are worth taking
+                for (uint32_t j = 0; j < 9u; ++j) {
+                    const uint32_t v = c[region_halo_index(best)];
+                    if (v >= best) break;
+                    best = v;
+                }
+            }
+            const bool lower = best < mine;
+            if (!__syncthreads_or(lower)) {
+                settled = true;
+                break;
+            }
+            if (lower) c[me] = mine = best;
+            __syncthreads();
+        }
+        if (!settled && tid == 0u) atomicAdd(counters + rtq::REGION_CNT_FAULT, 1u);
+        if (exists) {
+            const uint32_t i = row * g.nx + ix;
+            uint32_t root = rtq::kRegionNone;
+            if (in) {
+                const uint32_t rx = mine % rtq::kPathTileX, ry = mine / rtq::kPathTileX % rtq::kPathTileY,
+                               rz = mine / (rtq::kPathTileX * rtq::kPathTileY);
+                root = ((z0 + rz) * g.ny + y0 + ry) * g.nx + x0 + rx;
+            }
+            label[i] = root;
+            if (counts) counts[i] = 0u;
+        }
+    }
+}
+
+// A thread a point.  Each member takes each of its backward links (rtq::region_backward_move: 13 of the 26 moves, 3
+// of the 6) that leave its tile and unites the two trees (rtq::region_unite).  The links inside a tile are
+// k_regionlocal's, and every link between two tiles is backward from one of its ends, so after this launch two
+// members are in one tree iff they are in one region.  Of a run of parallel links along a row only the first is
+// united (below): in open space that leaves a link a row and move, not a link a point and move.
+__global__ void __launch_bounds__(rtq::kDistThreads) k_regionmerge(const uint32_t* __restrict__ member, uint32_t* label,
+                                                                  uint32_t* counters, RegionGrid g)
+{
+    const uint32_t words = (g.nx + 31u) / 32u, moves = rtq::region_backward_count(g.faces ? 6u : 26u);
+    RegionForest f{label, counters + rtq::REGION_CNT_FAULT};
+    for (uint32_t i = blockIdx.x * rtq::kDistThreads + threadIdx.x; i < g.points; i += gridDim.x * rtq::kDistThreads) {
+        const uint32_t row = i / g.nx, ix = i - row * g.nx, iz = row / g.ny, iy = row - iz * g.ny;
+        const uint32_t mine = member[row * words + (ix >> 5)], lx = ix & 31u;
+        if (!((mine >> lx) & 1u)) continue;
+        const bool run = lx && ((mine >> (lx - 1u)) & 1u); // the point before in the row is a member of this tile
+        for (uint32_t k = 0; k < moves; ++k) {
+            int dx, dy, dz;
+            rtq::region_backward_move(g.faces ? 6u : 26u, k, &dx, &dy, &dz);
+            const uint32_t qx = ix + (uint32_t)dx, qy = iy + (uint32_t)dy, qz = iz + (uint32_t)dz; // below 0 wraps: >= dim
+            if (qx >= g.nx || qy >= g.ny || qz >= g.nz) continue;
+            if (qx / rtq::kPathTileX == ix / rtq::kPathTileX && qy / rtq::kPathTileY == iy / rtq::kPathTileY &&
+                qz / rtq::kPathTileZ == iz / rtq::kPathTileZ)
+                continue; // inside the tile: k_regionlocal's
+            const uint32_t qrow = qz * g.ny + qy;
+            const uint32_t theirs = member[qrow * words + (qx >> 5)], qlx = qx & 31u;
+            if (!((theirs >> qlx) & 1u)) continue;
+            // The same link one point back along the row, from p - 1 to q - 1, joins the same two trees when both are
+            // members of the same two tiles: p - 1 and p are face neighbours in one tile, q - 1 and q in the other, and
+            // k_regionlocal has put each pair into one tree.  So only the first link of such a run is united.
+            if (run && qlx && ((theirs >> (qlx - 1u)) & 1u)) continue;
+            rtq::region_unite(f, i, qrow * g.nx + qx, g.points);
+        }
+    }
+}
+
+// One block a tile, a thread a point: label[p] = find(p), the root, which is the region's smallest index because a
+// parent is never above its child.  No tree changes its root in this launch; a word falls to its root and is read
+// by other finds on the way, old or new.  Then the counts (counts not null): the members of a wave that share the
+// first lane's root add once to the tile's table in LDS (keyed by root, open addressing over 512 slots for 512
+// points at most, so a free or equal slot is found within 512 probes), the others each for themselves, and the
+// tile issues one global atomic per root it holds.  The largest region usually holds nearly every member: a global
+// atomic a point would serialise on one word.
+__global__ void __launch_bounds__(rtq::kPathTilePoints) k_regionflatten(const uint32_t* __restrict__ member, uint32_t* label,
+                                                                       uint32_t* counts, uint32_t* counters, RegionGrid g)
+{
+    __shared__ uint32_t key[rtq::kPathTilePoints], val[rtq::kPathTilePoints];
+    const uint32_t tid = threadIdx.x, words = (g.nx + 31u) / 32u;
+    const uint32_t lx = tid % rtq::kPathTileX, ly = tid / rtq::kPathTileX % rtq::kPathTileY,
+                   lz = tid / (rtq::kPathTileX * rtq::kPathTileY);
+    RegionForest f{label, counters + rtq::REGION_CNT_FAULT};
+    for (uint32_t t = blockIdx.x; t < g.tiles; t += gridDim.x) {
+        const uint32_t tx = t % g.tnx, ty = t / g.tnx % g.tny, tz = t / (g.tnx * g.tny);
+        const uint32_t ix = tx * rtq::kPathTileX + lx, iy = ty * rtq::kPathTileY + ly, iz = tz * rtq::kPathTileZ + lz;
+        const uint32_t row = iz * g.ny + iy;
+        const bool in = iy < g.ny && iz < g.nz && ((member[row * words + tx] >> lx) & 1u);
+        uint32_t root = rtq::kRegionNone;
+        if (in) {
+            const uint32_t i = row * g.nx + ix;
+            root = rtq::region_find(f, i, g.points);
+            if (root != i) __hip_atomic_store(label + i, root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if (!counts) continue;
+        __syncthreads(); // the tile before is done with the table
+        key[tid] = rtq::kRegionNone;
+        val[tid] = 0u;
+        __syncthreads();
+        const uint32_t first = __shfl(root, __builtin_ctzll(__ballot(in) | (1ull << 63)), 64);
+        const uint64_t same = __ballot(in && root == first);
+        const bool leader = in && root == first && (uint32_t)__builtin_ctzll(same) == (tid & 63u);
+        if (in && (leader || root != first)) {
+            const uint32_t add = leader ? (uint32_t)__popcll(same) : 1u;
+            uint32_t slot = root % rtq::kPathTilePoints;
+            bool placed = false;
+            for (uint32_t probe = 0; probe < rtq::kPathTilePoints; ++probe) {
+                const uint32_t old = atomicCAS(&key[slot], rtq::kRegionNone, root);
+                if (old == rtq::kRegionNone || old == root) {
+                    atomicAdd(&val[slot], add);
+                    placed = true;
+                    break;
+                }
+                slot = (slot + 1u) % rtq::kPathTilePoints;
+            }
+            if (!placed) f.fault();
+        }
+        __syncthreads();
+        if (key[tid] != rtq::kRegionNone) atomicAdd(counts + key[tid], val[tid]);
+    }
+}
+
+// A thread a point: size[p] = the count at p's root (0 at a non-member), and the status: the roots, the members
+// and the largest count by a reduction in the wave and then in the block, and an atomic a block and word where the
+// block has something to add (every block adds to the same three words); status[0] from the fault counter.
+// label and counts are final when this launch starts.
+__global__ void __launch_bounds__(rtq::kDistThreads) k_regionfinish(const uint32_t* __restrict__ label, const uint32_t* __restrict__ counts,
+                                                                   uint32_t* __restrict__ size, const uint32_t* counters,
+                                                                   uint32_t* status, RegionGrid g)
+{
+    uint32_t regions = 0u, members = 0u, largest = 0u;
+    for (uint32_t i = blockIdx.x * rtq::kDistThreads + threadIdx.x; i < g.points; i += gridDim.x * rtq::kDistThreads) {
+        const uint32_t l = label[i];
+        const uint32_t n = l < g.points ? counts[l] : 0u; // (kRegionNone is no point)
+        if (size) size[i] = n;
+        members += l != rtq::kRegionNone;
+        if (l == i) {
+            ++regions;
+            largest = max(largest, n);
+        }
+    }
+    if (!status) return; // (the same in every thread)
+    __shared__ uint32_t part[3][rtq::kDistThreads / 64u];
+    for (int off = 32; off > 0; off >>= 1) {
+        regions += __shfl_down(regions, off, 64);
+        members += __shfl_down(members, off, 64);
+        largest = max(largest, (uint32_t)__shfl_down(largest, off, 64));
+    }
+    if ((threadIdx.x & 63u) == 0u) {
+        part[0][threadIdx.x / 64u] = regions;
+        part[1][threadIdx.x / 64u] = members;
+        part[2][threadIdx.x / 64u] = largest;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0u) return;
+    // the words are shared by every block: an atomic only where this block has something to add
+    regions = members = largest = 0u;
+    for (uint32_t w = 0; w < rtq::kDistThreads / 64u; ++w) {
+        regions += part[0][w];
+        members += part[1][w];
+        largest = max(largest, part[2][w]);
+    }
+    if (regions) atomicAdd(status + 1, regions);
+    if (members) atomicAdd(status + 2, members);
+    if (largest) atomicMax(status + 3, largest);
+    if (blockIdx.x == 0) status[0] = counters[rtq::REGION_CNT_FAULT] == 0u ? 1u : 0u;
+}
+
+} // namespace
+
+bool rt_launch_regionquery(const RtLaunch& a, const RtRegionQuery& q)
+{
+    const uint64_t points = (uint64_t)q.dims[0] * q.dims[1] * q.dims[2];
+    if (points == 0 || points > (1u << 26) || q.tile_blocks == 0 || q.point_blocks == 0) return false;
+    if (q.dims[0] > rtq::kMaxLatticeDim || q.dims[1] > rtq::kMaxLatticeDim || q.dims[2] > rtq::kMaxLatticeDim) return false;
+    if (!q.occupancy || !q.member || !q.counters || !q.label) return false;
+    if ((q.solid && q.d2) || (!q.counts && (q.size || q.status)) || (q.counts && !q.size && !q.status)) return false;
+    const rtq::PathTiles t = rtq::path_tiles(q.dims);
+    const RegionGrid g{q.dims[0], q.dims[1], q.dims[2], (uint32_t)points, t.n[0], t.n[1], t.n[2], t.total, q.faces ? 1u : 0u};
+    const dim3 tgrid(q.tile_blocks), tblock(rtq::kPathTilePoints), pgrid(q.point_blocks), pblock(rtq::kDistThreads);
+    hipLaunchKernelGGL(k_regionlocal, tgrid, tblock, 0, a.stream, q.occupancy, q.d2, q.member, q.label, q.counts, q.counters,
+                       q.status, q.solid ? 1u : 0u, g);
+    hipLaunchKernelGGL(k_regionmerge, pgrid, pblock, 0, a.stream, q.member, q.label, q.counters, g);
+    hipLaunchKernelGGL(k_regionflatten, tgrid, tblock, 0, a.stream, q.member, q.label, q.counts, q.counters, g);
+    if (q.counts)
+        hipLaunchKernelGGL(k_regionfinish, pgrid, pblock, 0, a.stream, q.label, q.counts, q.size, q.counters, q.status, g);
     return true;
 }
 

@@ -5,7 +5,7 @@
 // grids and mask arithmetic of rt_terrain_extract_mesh.  No HIP in here (the mask arithmetic is marked
 // __host__ __device__ under hipcc only, for k_meshcount): tests/tools/rayquery_check.cpp, surfquery_check.cpp,
 // shadequery_check.cpp, pointquery_check.cpp, fieldquery_check.cpp, meshquery_check.cpp, distquery_check.cpp,
-// pathquery_check.cpp, visquery_check.cpp and querylayout_check.cpp
+// pathquery_check.cpp, visquery_check.cpp, regionquery_check.cpp and querylayout_check.cpp
 // drive it stand-alone under ASan + UBSan.
 #pragma once
 
@@ -1022,6 +1022,179 @@ inline VisibilityPlan plan_visibility(uint32_t points, uint32_t max_blocks, int 
 {
     VisibilityPlan p;
     p.blocks = plan_distance(points, max_blocks, cus).blocks;
+    return p;
+}
+
+// ---- region fields (rt_terrain_region_field): the connected regions of the free or of the blocked points ----
+//
+// A union-find over the path field's tiles in a fixed number of launches, with `label` itself as the forest: word p
+// holds the index of another point of p's region that is not above p (its parent), p itself at a root, kRegionNone
+// at a non-member.  k_regionlocal forms the member words and labels every tile on its own in LDS, so label[p] is
+// the tile-local root; k_regionmerge unites the trees over every link that leaves a tile; k_regionflatten stores
+// find(p) in every word and counts the points of every root; k_regionfinish writes the sizes and the status.
+// region_find and region_unite below are what the kernels run and what tests/tools/regionquery_check.cpp runs.
+//
+// The invariant everything rests on: a forest word only ever falls, and only to the index of a point of the same
+// final region.  A read that returns an older value therefore returns an older ancestor of the same tree: it costs
+// steps, never correctness.
+
+constexpr uint32_t kRegionNone = 0xffffffffu; // RT_REGION_NONE
+// the first version of rt_region_options: size, flags, eye[3], max_blocks, clearance_cells, connectivity, state
+constexpr uint32_t kRegionOptSizeV1 = 36u;
+enum { REGION_FREE = 0, REGION_SOLID = 1 };
+
+struct RegionOptions : Options {
+    uint32_t clearance_cells = 0, connectivity = 26, state = REGION_FREE; // (connectivity 0 is read as 26)
+};
+
+// `opt` is the caller's rt_region_options (may be null: the defaults), read as far as the first version reaches.
+inline int parse_region_options(const void* opt, RegionOptions* out, const char** why)
+{
+    *out = RegionOptions{};
+    if (!opt) return OK;
+    if (!parse_prefix(opt, kRegionOptSizeV1, out)) {
+        *why = "rt_region_options.size is smaller than the struct's first version";
+        return INVALID;
+    }
+    if (out->flags & ~kEye) {
+        *why = "rt_region_options.flags has bits other than RT_RAYS_EYE";
+        return INVALID;
+    }
+    const char* p = static_cast<const char*>(opt);
+    std::memcpy(&out->clearance_cells, p + 24, 4);
+    std::memcpy(&out->connectivity, p + 28, 4);
+    std::memcpy(&out->state, p + 32, 4);
+    if (out->clearance_cells > kPathMaxClearance) {
+        *why = "rt_region_options.clearance_cells is above 4095";
+        return INVALID;
+    }
+    if (out->connectivity == 0u) out->connectivity = 26u;
+    if (out->connectivity != 6u && out->connectivity != 26u) {
+        *why = "rt_region_options.connectivity is not 0, 6 or 26";
+        return INVALID;
+    }
+    if (out->state > (uint32_t)REGION_SOLID) {
+        *why = "rt_region_options.state is not 0 (free) or 1 (solid)";
+        return INVALID;
+    }
+    if (out->state == (uint32_t)REGION_SOLID && out->clearance_cells) {
+        *why = "rt_region_options.clearance_cells must be 0 with state 1 (solid)";
+        return INVALID;
+    }
+    return OK;
+}
+
+// The backward moves: the moves whose neighbour has the smaller linear index, so that every link is taken once, from
+// its larger end.  Of the 26 moves they are the path field's codes 0..12 (the codes below "stay"), of the 6 face
+// moves the codes 4, 10 and 12: (0, 0, -1), (0, -1, 0), (-1, 0, 0).  With their negations they are all the moves.
+RTQ_HD inline uint32_t region_backward_count(uint32_t connectivity) { return connectivity == 6u ? 3u : 13u; }
+RTQ_HD inline void region_backward_move(uint32_t connectivity, uint32_t k, int* dx, int* dy, int* dz)
+{
+    path_move(connectivity == 6u ? (k == 0u ? 4u : k == 1u ? 10u : 12u) : k, dx, dy, dz);
+}
+
+// The root of x's tree, with path halving.  A: the access policy of the forest words, with
+//   uint32_t load(uint32_t i)              the word of point i (on the device a relaxed load at agent scope),
+//   uint32_t fall(uint32_t i, uint32_t v)  word i = min(word i, v), the word's value before (on the device atomicMin),
+//   void fault()                           a fail-safe bound ended a loop.
+// x is a member.  Variant: x, which strictly falls (a parent is below its child); the bound, the lattice's points at
+// most, can therefore not be hit by a forest; if it is hit the loop ends all the same.
+template <class A>
+RTQ_HD inline uint32_t region_find(A& a, uint32_t x, uint32_t bound)
+{
+    for (uint32_t k = 0; k < bound; ++k) {
+        const uint32_t p = a.load(x);
+        if (p >= x) return x; // a root (a forest holds no word above its index)
+        const uint32_t g = a.load(p);
+        if (g >= p) return p;
+        a.fall(x, g); // halving: g is an ancestor of x, below the word's value; another thread may have lowered it more
+        x = g;
+    }
+    a.fault();
+    return x;
+}
+
+// Unite the trees of the members x and y, lock-free: find both roots, let the larger root's word fall to the
+// smaller root, and if the word had already fallen (another thread got there first, or the root that was read was
+// an older value) go on from the value it held: that is a point of the same tree below the root.  Variant: the
+// larger of the two roots, which strictly falls from one round to the next; the bound as in region_find.
+template <class A>
+RTQ_HD inline void region_unite(A& a, uint32_t x, uint32_t y, uint32_t bound)
+{
+    for (uint32_t k = 0; k < bound; ++k) {
+        x = region_find(a, x, bound);
+        y = region_find(a, y, bound);
+        if (x == y) return;
+        if (x < y) {
+            const uint32_t t = x;
+            x = y;
+            y = t;
+        }
+        const uint32_t old = a.fall(x, y); // x > y
+        if (old >= x) return;              // x was a root and hangs below y now
+        x = old;
+    }
+    a.fault();
+}
+
+// the forest as a plain array: the stand-alone checker's policy (one thread)
+struct RegionHostForest {
+    uint32_t* w;
+    uint32_t faults = 0;
+    uint32_t load(uint32_t i) { return w[i]; }
+    uint32_t fall(uint32_t i, uint32_t v)
+    {
+        const uint32_t old = w[i];
+        if (v < old) w[i] = v;
+        return old;
+    }
+    void fault() { ++faults; }
+};
+
+// the counters of a region field, the last part of its scratch block (uint32 each)
+enum {
+    REGION_CNT_FAULT = 0,  // loops that a fail-safe bound ended: status[0] is 1 while this is 0
+    REGION_CNT_STATUS = 8, // [4]: the host form's status words
+    REGION_CNT_WORDS = 16
+};
+
+// The scratch block of a region field, laid out by block_layout: the lattice's occupancy words (used when the
+// terrain's own occupancy is asked for); with a clearance the distance field's scratch block followed by its d2, a
+// uint32 a point; the member words; the region counts, a uint32 a point (the count of a region at its root's
+// index); the counters.
+struct RegionScratch {
+    uint32_t points = 0;
+    PathTiles tiles;
+    size_t d2_offset = 0; // of d2 within the REGION_DISTANCE part
+    BlockLayout lay;      // total 0 without points
+};
+enum { REGION_OCCUPANCY = 0, REGION_DISTANCE = 1, REGION_MEMBER = 2, REGION_COUNTS = 3, REGION_COUNTERS = 4 };
+
+// dims of a lattice that check_lattice passed
+inline RegionScratch region_scratch(const uint32_t dims[3], uint32_t clearance_cells)
+{
+    RegionScratch s;
+    s.points = dims[0] * dims[1] * dims[2];
+    if (s.points == 0) return s;
+    s.tiles = path_tiles(dims);
+    s.d2_offset = clearance_cells ? distance_scratch(dims).lay.total : 0;
+    const size_t bytes[5] = {occupancy_bytes(dims), clearance_cells ? s.d2_offset + (size_t)s.points * 4 : 0,
+                             occupancy_bytes(dims), (size_t)s.points * 4, (size_t)REGION_CNT_WORDS * 4};
+    s.lay = block_layout(bytes, 5);
+    return s;
+}
+
+// The grids: k_regionlocal and k_regionflatten a block of kPathTilePoints threads a tile, striding over the tiles,
+// four blocks a CU resident, as the path sweep; k_regionmerge and k_regionfinish a thread a point as the distance
+// passes.
+struct RegionPlan {
+    uint32_t tile_blocks = 0, point_blocks = 0;
+};
+inline RegionPlan plan_region(const RegionScratch& s, uint32_t max_blocks, int cus)
+{
+    RegionPlan p;
+    p.tile_blocks = field_grid(s.tiles.total, max_blocks, 4 * (cus > 0 ? cus : 1));
+    p.point_blocks = plan_distance(s.points, max_blocks, cus).blocks;
     return p;
 }
 

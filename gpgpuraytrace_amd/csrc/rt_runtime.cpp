@@ -3678,6 +3678,27 @@ extern "C" int rt_terrain_distance_field_device(rt_compute c, const rt_lattice* 
 // (rt_launch_pathquery), all on the device stream.
 namespace {
 
+// The clearance of a path or region field: the distance field's own passes, unchanged, with max_cells the
+// clearance, into `part` (the distance scratch block followed by d2 at d2_offset): passable is a far d2.
+int clearance_enqueue(rt_device dev, const RtLaunch& a, const rtq::Lattice& l, uint32_t points, uint32_t clearance_cells,
+                      uint32_t max_blocks, const void* occupancy, char* part, size_t d2_offset, const uint32_t** d2)
+{
+    const rtq::DistanceScratch ds = rtq::distance_scratch(l.dims);
+    RtDistanceQuery dq{};
+    dq.occupancy = (const uint32_t*)occupancy;
+    dq.rows = (uint32_t*)(part + ds.lay.offset[rtq::DIST_ROWS]);
+    dq.planes = (uint32_t*)(part + ds.lay.offset[rtq::DIST_PLANES]);
+    memcpy(dq.dims, l.dims, sizeof(dq.dims));
+    const rtq::DistanceBound b = rtq::distance_bound(clearance_cells);
+    dq.reach = b.reach;
+    dq.limit2 = b.limit2;
+    dq.d2 = (uint32_t*)(part + d2_offset);
+    dq.blocks = rtq::plan_distance(points, max_blocks, cus_of(dev)).blocks;
+    if (int rc = query_launched(rt_launch_distancequery(a, dq), "no kernel for the clearance's distance passes")) return rc;
+    *d2 = dq.d2;
+    return RT_OK;
+}
+
 // the host form keeps its status words behind the counters the kernels use
 constexpr size_t kPathHostStatus = 8;
 static_assert(kPathHostStatus + 4 <= (size_t)rtq::PATH_CNT_WORDS, "the status words lie within the counters' part");
@@ -3699,23 +3720,10 @@ int path_field_enqueue(rt_compute c, const rtq::Lattice& l, const rtq::PathScrat
     }
     const RtLaunch a = make_launch(dev, c->shader);
     const uint32_t* d2 = nullptr;
-    if (o.clearance_cells) {
-        // the distance field's own passes, unchanged, with max_cells the clearance: passable is a far d2
-        char* part = scratch + s.lay.offset[rtq::PATH_DISTANCE];
-        const rtq::DistanceScratch ds = rtq::distance_scratch(l.dims);
-        RtDistanceQuery dq{};
-        dq.occupancy = (const uint32_t*)occupancy;
-        dq.rows = (uint32_t*)(part + ds.lay.offset[rtq::DIST_ROWS]);
-        dq.planes = (uint32_t*)(part + ds.lay.offset[rtq::DIST_PLANES]);
-        memcpy(dq.dims, l.dims, sizeof(dq.dims));
-        const rtq::DistanceBound b = rtq::distance_bound(o.clearance_cells);
-        dq.reach = b.reach;
-        dq.limit2 = b.limit2;
-        dq.d2 = (uint32_t*)(part + s.d2_offset);
-        dq.blocks = rtq::plan_distance(s.points, o.max_blocks, cus_of(dev)).blocks;
-        if (int rc = query_launched(rt_launch_distancequery(a, dq), "rt_terrain_path_field: no kernel for the clearance")) return rc;
-        d2 = dq.d2;
-    }
+    if (o.clearance_cells)
+        if (int rc = clearance_enqueue(dev, a, l, s.points, o.clearance_cells, o.max_blocks, occupancy,
+                                       scratch + s.lay.offset[rtq::PATH_DISTANCE], s.d2_offset, &d2))
+            return rc;
     const rtq::PathPlan plan = rtq::plan_path(s, o.max_blocks, cus_of(dev));
     uint32_t* counters = (uint32_t*)(scratch + s.lay.offset[rtq::PATH_COUNTERS]);
     RtPathQuery q{};
@@ -3946,6 +3954,119 @@ extern "C" int rt_terrain_visibility_field_device(rt_compute c, const rt_lattice
 {
     return visibility_field_entry("rt_terrain_visibility_field_device", c, lat, opt, occupancy_in_device, observers_device,
                                   n_observers, scratch_device, scratch_bytes, mask_device, status_device, false);
+}
+
+// ---------------------------------------------------------------------------
+// rt_terrain_region_field: for every point the smallest index of its connected region of free or of blocked points,
+// and optionally the region's size (include/frosttrace.h): the caller's occupancy words, or the lattice query's
+// occupancy pass into the scratch block; with a clearance the distance passes; then the union-find's launches
+// (rt_launch_regionquery), three when neither size nor status is asked for and four otherwise, on the device stream.
+namespace {
+
+static_assert((size_t)rtq::REGION_CNT_STATUS + 4 <= (size_t)rtq::REGION_CNT_WORDS, "the status words lie within the counters' part");
+
+// Enqueue one region field (no host synchronisation, no allocation); the scratch block holds s.lay.total bytes;
+// occupancy null: the terrain's own.  host: the status words stay in the scratch block's counters and are copied
+// to `status` (host memory) from there.
+int region_field_enqueue(rt_compute c, const rtq::Lattice& l, const rtq::RegionScratch& s, const rtq::RegionOptions& o,
+                         const void* occupancy, char* scratch, void* label, void* size, void* status, bool host)
+{
+    rt_device dev = c->dev;
+    if (!occupancy) {
+        rtq::FieldOptions occ_opt = o; // the eye and the grid's cap
+        void* own = scratch + s.lay.offset[rtq::REGION_OCCUPANCY];
+        if (int rc = sample_field_enqueue(c, nullptr, &l, s.points, occ_opt, nullptr, own)) return rc;
+        occupancy = own;
+    }
+    const RtLaunch a = make_launch(dev, c->shader);
+    const uint32_t* d2 = nullptr;
+    if (o.clearance_cells)
+        if (int rc = clearance_enqueue(dev, a, l, s.points, o.clearance_cells, o.max_blocks, occupancy,
+                                       scratch + s.lay.offset[rtq::REGION_DISTANCE], s.d2_offset, &d2))
+            return rc;
+    uint32_t* counters = (uint32_t*)(scratch + s.lay.offset[rtq::REGION_COUNTERS]);
+    // the fault counter starts from 0: zeroed on the stream the kernels run on, so the two are ordered
+    HIP_TRY(hipMemsetAsync(counters, 0, (size_t)rtq::REGION_CNT_WORDS * 4, dev->stream));
+    const rtq::RegionPlan plan = rtq::plan_region(s, o.max_blocks, cus_of(dev));
+    RtRegionQuery q{};
+    q.occupancy = (const uint32_t*)occupancy;
+    q.d2 = d2;
+    q.member = (uint32_t*)(scratch + s.lay.offset[rtq::REGION_MEMBER]);
+    q.counters = counters;
+    memcpy(q.dims, l.dims, sizeof(q.dims));
+    q.solid = o.state == (uint32_t)rtq::REGION_SOLID;
+    q.faces = o.connectivity == 6u;
+    q.label = (uint32_t*)label;
+    q.size = (uint32_t*)size;
+    q.status = !status ? nullptr : host ? counters + rtq::REGION_CNT_STATUS : (uint32_t*)status;
+    q.counts = size || status ? (uint32_t*)(scratch + s.lay.offset[rtq::REGION_COUNTS]) : nullptr;
+    q.tile_blocks = plan.tile_blocks;
+    q.point_blocks = plan.point_blocks;
+    if (int rc = query_launched(rt_launch_regionquery(a, q), "rt_terrain_region_field: no kernel for this query")) return rc;
+    if (host && status) HIP_TRY(hipMemcpyAsync(status, q.status, 16, hipMemcpyDeviceToHost, dev->stream));
+    return RT_OK;
+}
+
+// both entry points; host: the blocking form, whose arrays are the host's
+int region_field_entry(const char* who, rt_compute c, const rt_lattice* lat, const rt_region_options* opt, const void* occupancy,
+                       void* scratch, size_t scratch_bytes, void* label, void* size, void* status, bool host)
+{
+    const QueryFamily<rtq::RegionOptions> f{who, nullptr, rtq::parse_region_options};
+    rtq::Lattice l;
+    rtq::RegionScratch s;
+    std::string missing = std::string(who) + ": label is null";
+    return query_entry(
+        c, f, 0, opt,
+        [&](const rtq::RegionOptions& o, uint32_t* n) -> int {
+            const char* why = "";
+            if (int rc = rtq::check_lattice(lat, &l, n, &why)) return fail(rc, "%s: %s", who, why);
+            s = rtq::region_scratch(l.dims, o.clearance_cells);
+            if (!host && *n) {
+                if (!scratch || scratch_bytes < s.lay.total)
+                    return fail(RT_ERR_INVALID, "%s: the scratch block is null or below rt_terrain_region_scratch_bytes", who);
+                if (((uintptr_t)scratch | (uintptr_t)occupancy | (uintptr_t)label | (uintptr_t)size | (uintptr_t)status) % 4)
+                    return fail(RT_ERR_INVALID, "%s: the device arrays must be 4-byte aligned", who);
+            }
+            return RT_OK;
+        },
+        !label ? missing.c_str() : nullptr,
+        [&](const rtq::RegionOptions& o, uint32_t n) {
+            if (!host) return region_field_enqueue(c, l, s, o, occupancy, (char*)scratch, label, size, status, false);
+            // one device block: the scratch, the caller's occupancy words, the two results
+            const HostPart parts[] = {{s.lay.total, nullptr, nullptr},
+                                      {occupancy ? rtq::occupancy_bytes(l.dims) : 0, occupancy, nullptr},
+                                      {(size_t)n * 4, nullptr, label},
+                                      {size ? (size_t)n * 4 : 0, nullptr, size}};
+            return host_form(c->dev, parts, [&](char* const* at) {
+                return region_field_enqueue(c, l, s, o, at[1], at[0], at[2], at[3], status, true);
+            });
+        });
+}
+
+} // namespace
+
+extern "C" size_t rt_terrain_region_scratch_bytes(const rt_lattice* lat, const rt_region_options* opt)
+{
+    rtq::Lattice l;
+    rtq::RegionOptions o;
+    uint32_t n = 0;
+    const char* why = "";
+    if (rtq::check_lattice(lat, &l, &n, &why) || rtq::parse_region_options(opt, &o, &why)) return 0;
+    return rtq::region_scratch(l.dims, o.clearance_cells).lay.total;
+}
+
+extern "C" int rt_terrain_region_field(rt_compute c, const rt_lattice* lat, const rt_region_options* opt,
+                                       const uint32_t* occupancy_in, uint32_t* label, uint32_t* size, uint32_t status[4])
+{
+    return region_field_entry("rt_terrain_region_field", c, lat, opt, occupancy_in, nullptr, 0, label, size, status, true);
+}
+
+extern "C" int rt_terrain_region_field_device(rt_compute c, const rt_lattice* lat, const rt_region_options* opt,
+                                              const void* occupancy_in_device, void* scratch_device, size_t scratch_bytes,
+                                              void* label_device, void* size_device, void* status_device)
+{
+    return region_field_entry("rt_terrain_region_field_device", c, lat, opt, occupancy_in_device, scratch_device, scratch_bytes,
+                              label_device, size_device, status_device, false);
 }
 
 // ---------------------------------------------------------------------------

@@ -1042,6 +1042,78 @@ class Terrain:
                                                       status_ptr or None)
         return rc == _native.RT_OK
 
+    def region_field(self, origin, spacing, dims, eye=None, clearance=0, occupancy=None, connectivity=26, solid=False,
+                     sizes=False, max_blocks=0, status=None):
+        """rt_terrain_region_field: for every point of the lattice (sample_lattice's origin, spacing and dims) the
+        label of its connected region, an array shaped (nz, ny, nx) uint32: the smallest point index
+        (iz * ny + iy) * nx + ix of the region, RT_REGION_NONE where the point is no member.  Members are the free
+        points (with a clearance: those more than that many cells from every blocked point, as path_field's), or
+        with solid=True the blocked points.  connectivity: 26 (the path field's moves) or 6 (the face moves).
+        occupancy: None for the terrain's own, or bit words as sample_lattice returns them.  sizes=True:
+        (labels, sizes), sizes uint32 the number of points of the point's region, 0 at a non-member.  status: a
+        list that receives the four status words (completed, regions, members, the largest region's size).  None
+        if the call fails.  Blocking; uses the camerarays compute."""
+        lat, (nx, ny, nz) = lattice(origin, spacing, dims), (int(v) for v in dims)
+        opt = region_options(eye, clearance, connectivity, solid, max_blocks)
+        occ = None
+        if occupancy is not None:
+            occ = np.ascontiguousarray(occupancy, np.uint32)
+            if occ.size != nz * ny * ((nx + 31) // 32):
+                raise ValueError("region_field: occupancy must hold ceil(nx / 32) * ny * nz words")
+        self.update_shaders()
+        labels = np.empty((nz, ny, nx), np.uint32)
+        sz = np.empty((nz, ny, nx), np.uint32) if sizes else None
+        st = np.zeros(4, np.uint32)
+        rc = lib().rt_terrain_region_field(self.camera_compute._h, C.byref(lat), C.byref(opt),
+                                           occ.ctypes.data if occ is not None and occ.size else None, labels.ctypes.data,
+                                           sz.ctypes.data if sizes and sz.size else None,
+                                           st.ctypes.data if status is not None else None)
+        if rc != _native.RT_OK:
+            return None
+        if status is not None:
+            status[:] = [int(v) for v in st]
+        return (labels, sz) if sizes else labels
+
+    def region_field_device(self, origin, spacing, dims, scratch_ptr, scratch_bytes, label_ptr, size_ptr=0, status_ptr=0,
+                            occupancy_ptr=0, eye=None, clearance=0, connectivity=26, solid=False, max_blocks=0):
+        """rt_terrain_region_field_device: the same into device arrays -- scratch_ptr at least
+        region_scratch_bytes(origin, spacing, dims, clearance) bytes, label_ptr nx ny nz uint32, size_ptr the same or
+        0, status_ptr 4 uint32 or 0, occupancy_ptr the caller's bit words or 0 for the terrain's own -- a fixed
+        number of launches enqueued on the device's stream with no host synchronisation and no allocation.  True on
+        success."""
+        lat = lattice(origin, spacing, dims)
+        opt = region_options(eye, clearance, connectivity, solid, max_blocks)
+        self.update_shaders()
+        rc = lib().rt_terrain_region_field_device(self.camera_compute._h, C.byref(lat), C.byref(opt), occupancy_ptr or None,
+                                                  scratch_ptr or None, int(scratch_bytes), label_ptr or None,
+                                                  size_ptr or None, status_ptr or None)
+        return rc == _native.RT_OK
+
+
+def region_scratch_bytes(origin, spacing, dims, clearance=0):
+    """rt_terrain_region_scratch_bytes: the bytes of region_field_device's scratch block for a lattice and a
+    clearance (0 for an invalid lattice or one without points)."""
+    lat = lattice(origin, spacing, dims)
+    opt = region_options(clearance=clearance)
+    return int(lib().rt_terrain_region_scratch_bytes(C.byref(lat), C.byref(opt)))
+
+
+def region_options(eye=None, clearance=0, connectivity=26, solid=False, max_blocks=0):
+    """An rt_region_options block: the eye of the terrain's own occupancy (None: the compute's Eye), the clearance in
+    cells (free regions only), the connectivity (26, 6, or 0 for the default 26), the state (solid: the blocked
+    points), the grids' cap."""
+    opt = _native.RtRegionOptions()
+    opt.size = C.sizeof(_native.RtRegionOptions)
+    opt.flags = 0
+    if eye is not None:
+        opt.flags |= _native.RT_RAYS_EYE
+        opt.eye[:] = [float(x) for x in np.asarray(eye, np.float32).reshape(3)]
+    opt.max_blocks = int(max_blocks)
+    opt.clearance_cells = int(clearance)
+    opt.connectivity = int(connectivity)
+    opt.state = 1 if solid else 0
+    return opt
+
 
 def visibility_scratch_bytes(origin, spacing, dims):
     """rt_terrain_visibility_scratch_bytes: the bytes of visibility_field_device's scratch block for a lattice (0 for

@@ -930,6 +930,64 @@ int rt_terrain_visibility_field_device(rt_compute cs, const rt_lattice* lat, con
                                        const void* occupancy_in_device, const void* observers_device, uint32_t n_observers,
                                        void* scratch_device, size_t scratch_bytes, void* mask_device, void* status_device);
 
+/* ---- region fields (ABI 9, additive; no reference counterpart) ----
+ * Which points belong together: for every point of a lattice the label of its connected region of free space, or
+ * of the ground.  Is B reachable from A at all, which pockets are sealed off, which parts of the ground float, did a
+ * dig cut a region in two.  Formed on the device from the occupancy bits by a union-find in a fixed number of
+ * launches: no sweeps, and no sweep count for the caller to guess.  The answer is unique and independent of any
+ * order of work.
+ * The lattice is an rt_lattice exactly as rt_terrain_sample_lattice reads it; point index and occupancy word layout
+ *   as there.  A point is BLOCKED when its occupancy bit is set; the padding bits of a row's last word are ignored
+ *   whatever they hold.
+ *   occupancy_in NULL: the terrain's own occupancy, computed on the device into the scratch block as the distance
+ *     field does it (RT_RAYS_EYE and max_blocks as there, either kind of compute).
+ *   occupancy_in not NULL: the caller's words; the terrain is not evaluated.
+ * Members.  state 0 (free): a point is a MEMBER iff it is passable in rt_terrain_path_field's exact sense: not
+ *     blocked, and with clearance_cells = R > 0 its d2 greater than R * R, d2 exactly rt_terrain_distance_field's
+ *     (the unchanged distance passes at max_cells = R, into the scratch block).
+ *   state 1 (solid): a point is a member iff it is blocked.  clearance_cells must be 0, else RT_ERR_INVALID.
+ * Links.  connectivity 26 (0 means 26, the default) links two members that are one of the path field's 26 moves
+ *   apart; connectivity 6 links by the six face moves only.  A REGION is a class of the members under the links'
+ *   transitive closure.  For state 0 at connectivity 26 a region is therefore exactly a set of points with a finite
+ *   rt_terrain_path_field cost from one another.  There is no rule against a diagonal link between two non-members:
+ *   the path field's choice, with the same remedy (a clearance, or connectivity 6).
+ * Label (uint32 a point at index (iz * ny + iy) * nx + ix, required).  The smallest linear point index of the point's
+ *   region; RT_REGION_NONE at a non-member.  A point p is its region's root iff label[p] == p.
+ * Size (uint32 a point, optional; NULL is not written).  The number of points of the point's region, the same value
+ *   at every point of it; 0 at a non-member.
+ * Status (4 uint32; may be NULL in both forms): [0] 1 when the labelling completed, 0 when a fail-safe bound ended a
+ *   loop of a kernel (every loop there has a strictly decreasing integer as its variant and cannot reach its bound
+ *   on a forest; the bound is there because a kernel must end whatever it reads); [1] the number of regions; [2] the
+ *   number of member points; [3] the size of the largest region, 0 when there is none.
+ * opt (NULL: the defaults) is an rt_region_options: size >= 36, flags RT_RAYS_EYE or 0, eye, max_blocks (the cap of
+ *   every pass's grid, 0: none), clearance_cells (<= 4095), connectivity (0, 6 or 26), state (0 or 1).
+ * rt_terrain_region_scratch_bytes: the device form's scratch block for the lattice and opt->clearance_cells: the
+ *   occupancy words; with a clearance the distance scratch and a word a point for d2; the member words; a word a
+ *   point for the region counts; 64 bytes of counters; each part rounded up to 16 bytes.  0 for an invalid lattice
+ *   or option block, or a lattice without points.  The forest of the union-find is label itself and needs no part.
+ * rt_terrain_region_field: host arrays; blocking.  It uploads any given occupancy and downloads nothing but the
+ *   arrays asked for.
+ * rt_terrain_region_field_device: device arrays (4-byte aligned), enqueued on the compute's device stream; it
+ *   allocates nothing and never synchronises the host.  Three kernel launches after the occupancy and distance
+ *   passes when neither size nor status is asked for, four otherwise, whatever the lattice holds.
+ * Both: RT_ERR_INVALID for the lattice's errors (as rt_terrain_sample_lattice), a NULL compute, lattice or label,
+ *   opt->size < 36, flags other than RT_RAYS_EYE, clearance_cells > 4095, connectivity not 0, 6 or 26, state > 1,
+ *   state 1 with a clearance, and in the device form a scratch block that is NULL or below
+ *   rt_terrain_region_scratch_bytes; nothing is written then.  RT_ERR_STATE as for the distance field (texPerm2D
+ *   bound and the fail-safe word clear, with a given occupancy too).  A dims product of 0 is RT_OK and launches
+ *   nothing.  Like every query it reads no frame state and changes none.
+ * Out of scope: 18-connectivity; a compact, renumbered label set or a per-region table (bounding boxes, centroids);
+ *   labelling both states in one call; regions across two lattices; incremental relabelling after an edit; gravity
+ *   or walkable-surface regions. */
+#define RT_REGION_NONE 0xFFFFFFFFu
+typedef struct { uint32_t size, flags; float eye[3]; uint32_t max_blocks, clearance_cells, connectivity, state; } rt_region_options; /* 36 bytes, v1 */
+size_t rt_terrain_region_scratch_bytes(const rt_lattice* lat, const rt_region_options* opt);
+int rt_terrain_region_field(rt_compute cs, const rt_lattice* lat, const rt_region_options* opt, const uint32_t* occupancy_in,
+                            uint32_t* label, uint32_t* size, uint32_t status[4]);
+int rt_terrain_region_field_device(rt_compute cs, const rt_lattice* lat, const rt_region_options* opt,
+                                   const void* occupancy_in_device, void* scratch_device, size_t scratch_bytes,
+                                   void* label_device, void* size_device, void* status_device);
+
 /* ---- diagnostics (primitive-level parity tests; no reference counterpart) ----
  * rt_debug_math: device evaluation of the numeric primitives of DESIGN.md §Numerics
  *   (op 0 exp2, 1 log2, 2 exp, 3 sin, 4 cos, 5 sqrt, 6 rcp, 7 rsqrt, 8 pow, 9 max,
