@@ -5,7 +5,8 @@ Follows the HLSL line by line in double precision, as tests/sky_ref.py does for 
     Media/common/shaders/tracescreen.hlsl:16-48 (the hit and the miss composite of traceSample)
     Media/{nomadplains,simple,testing,greenrocks}/shaders/terrain.hlsl (getDensity, getFog)
     Media/{nomadplains,simple,testing,greenrocks}/shaders/color.hlsl (getColor)
-noise3d (noise.hlsl:139-179), getRayleighMieColor and getSpaceColor are sky_ref's.  A literal is its float32 value
+noise3d (noise.hlsl:139-179), getRayleighMieColor and getSpaceColor are sky_ref's, and so are the sky's literals
+("sky.*", listed in LITERALS here) and its structural misreadings ("sky.structure").  A literal is its float32 value
 widened to float64; everything else is real-number arithmetic (numpy `**`, log2, sqrt, sin, cos).  It shares no
 code, no fma rule and no polynomial with oracle/rt_oracle.c or rt_shader.h, so agreement within a tolerance pins
 their arithmetic to the HLSL's real-number meaning (tests/test_hlsl_kat.py, tests/test_gpu_hlsl_kat.py).
@@ -32,7 +33,8 @@ it stands); `tweak={name: value}` replaces it, which is how the mutation check o
 bounds notice a misread constant; the march's literals ("march.*") and the shadow ray's ("<land>.shadow.*") stand
 in the same table.  Some tweaks are not numbers: "march.structure" names one of MARCH_STRUCTURES, and
 "<land>.color.swizzle" ("yxz" by default) names the coordinates of p that the colour FBM's three factors multiply;
-"ao.structure" and "resolve.structure" name one of AO_STRUCTURES and RESOLVE_STRUCTURES.  The AO hash's literals
+"ao.structure", "resolve.structure" and "sky.structure" name one of AO_STRUCTURES, RESOLVE_STRUCTURES and
+sky_ref.STRUCTURES.  The AO hash's literals
 (INTEGER_LITERALS) are integers, printed in hexadecimal or decimal as DESIGN.md prints them, and are tweaked by
 Python integers.
 """
@@ -147,6 +149,10 @@ _lits("simple.color", "simple/shaders/color.hlsl:34", fade_from="200.0", fade_ov
 _lits("testing.color", "testing/shaders/color.hlsl:15", base_r="0.6", base_g="0.5", base_b="0.3", alpha="0.1")
 _lits("greenrocks.color", "greenrocks/shaders/color.hlsl:14", base_r="0.6", base_g="0.7", base_b="0.3", alpha="0.1")
 
+# the sky's literals ("sky.*") stand in sky_ref's table, which restates them; traceSample's own blend factor here
+LITERALS.update(S.LITERALS)
+_lits("sample", "common/shaders/tracescreen.hlsl:22", sky_amount="0.0005")
+
 SWIZZLES = ("nomadplains.color.swizzle", "simple.color.swizzle")
 # loop bounds printed with a fraction digit, which a change of that digit cannot move to another octave count
 OCTAVE_BOUNDS = ("simple.density.octaves", "greenrocks.density.a_octaves", "greenrocks.density.b_octaves")
@@ -160,7 +166,8 @@ def mutate(text):
 
 
 def mutants(prefix):
-    """(name, tweak) for every literal under `prefix` ("<land>.<density|fog|color>"), last digit changed by one;
+    """(name, tweak) for every literal under `prefix` ("<land>.<density|fog|color>", "march", "ao", "resolve", "sky",
+    "sample"), last digit changed by one;
     for an OCTAVE_BOUNDS literal one octave more as well ("<name>+1"), and for a colour FBM the swap of the two
     coordinates under the small factors."""
     for name, (text, _) in LITERALS.items():
@@ -412,10 +419,10 @@ def sample_color(land, pd, dens, fcolord, pdn, eye, sun, normals, shadowed, shad
     pd, fc = np.asarray(pd, np.float64).reshape(-1, 4), np.asarray(fcolord, np.float64).reshape(-1, 4)
     dens, pdn = np.asarray(dens, np.float64).reshape(-1), _vec(pdn)
     perm2d, grad = tab or tables()
-    sky_amount = pd[:, 3] * f32("0.0005")  # :22
+    sky_amount = pd[:, 3] * _K("sample", tweak)("sky_amount")  # :22
     sky_amount = _sat(sky_amount * sky_amount)[:, None]  # :23
-    mie, rayleigh = S.rayleigh_mie(pdn, np.asarray(eye, np.float64)[:3], sun)  # :25
-    sky = mie + rayleigh + S.space_color(perm2d, grad, pdn, sun)[:, None]  # :26-27
+    mie, rayleigh = S.rayleigh_mie(pdn, np.asarray(eye, np.float64)[:3], sun, tweak)  # :25
+    sky = mie + rayleigh + S.space_color(perm2d, grad, pdn, sun, tweak)[:, None]  # :26-27
     hit = dens > 0.0  # :29
     out = _lerp(_lerp(sky, fc[:, :3], fc[:, 3:4]), sky, sky_amount)  # :37-38
     unsafe = np.zeros(len(pd), bool)
@@ -484,12 +491,13 @@ MARCH_STRUCTURES = {
 }
 MARCH_FOG = ("march.mid_half", "march.structure=no_fog_refund", "march.structure=fog_by_laststep")
 TIE_BAND = 1e-5
-STRUCTURES = ("march.structure", "ao.structure", "resolve.structure")
+STRUCTURES = ("march.structure", "ao.structure", "resolve.structure", "sky.structure")
 
 
 def _march_mutants(prefix):
     """The structural misreadings of a prefix that has some: "<prefix>.structure=<name>"."""
-    for s in {"march": MARCH_STRUCTURES, "ao": AO_STRUCTURES, "resolve": RESOLVE_STRUCTURES}.get(prefix, ()):
+    for s in {"march": MARCH_STRUCTURES, "ao": AO_STRUCTURES, "resolve": RESOLVE_STRUCTURES,
+              "sky": S.STRUCTURES}.get(prefix, ()):
         yield prefix + ".structure=" + s, {prefix + ".structure": s}
 
 
@@ -616,7 +624,7 @@ _lits("ao", _T + ", the factor", strength="0.6")
 _lits("resolve", "common/shaders/tracescreen.hlsl:63", start="0.0")
 _lits("resolve", "common/shaders/tracescreen.hlsl:75", alpha="1.0")
 INTEGER_LITERALS = tuple("ao." + k for k in ("key_px", "key_py", "key_k", "pack", "pcg_mul", "pcg_add", "pcg_out",
-                                             "shift_top", "shift_base", "shift_out", "shift_u"))
+                                             "shift_top", "shift_base", "shift_out", "shift_u")) + S.INTEGER_LITERALS
 AO_STRUCTURES = {
     "swap_u": "u1 and u2 exchanged",
     "uniform_hemisphere": "sz = 1 - u1, r = sqrt(1 - sz^2): uniform over the hemisphere, not cosine-weighted",
